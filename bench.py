@@ -4,7 +4,7 @@
     stereo pairs/sec (540x960, D=192) fwd+bwd     [configs[1]: batch 4 per GPU,
     PSMNet, supervised disparity loss only, Adam step included]
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,9 +12,18 @@ One process per GPU; N>1 shards pairs across ranks (data parallel, RCCL gradient
 all-reduce through DistributedDataParallel), weak scaling: batch 4 per GPU.
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
 
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.
+--full adds the measurements that take time of their own: the per-kernel roofline
+(HIP events around the kernels of the timed steps, the stand-alone V0 probe, the HBM
+copy probe), the PyTorch-eager legs and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float32; a fixed, seeded sample of an array when all of them would exceed 60 MB).
+
 Synthetic data: rand images, ImageNet-normalised, 540 rows padded
 to 544 on top as test.py does; smooth ground-truth disparity in (5,185); weights
-from the reference init rule under manual_seed(1).
+from the reference init rule under manual_seed(1).  Every warm-up and timed step is
+the same training step (fwd + loss + bwd + Adam) from the same initial model and
+optimizer state (InitialState), so that a run computes the same thing every time.
 """
 import argparse
 import json
@@ -46,6 +55,11 @@ def parse():
                          "reprojection loss) then real step (reprojection loss only), 6-channel PSMNet; "
                          "raft = configs[4]'s hot path: CorrBlock1D volume + pyramid at [B,256,H/4,W/4], then 22 x "
                          "(4-level lookup + ConvGRU update at the 1/4 resolution), forward + backward")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline / per-kernel figures, the "
+                         "PyTorch-eager legs and the CPU baseline (the --no-* and --eager-* options below apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32, 60 MB at most)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager-steps", type=int, default=1,
                     help="timed steps of the same workload on stock PyTorch-ROCm operators (tools/eager_psmnet.py) "
@@ -111,6 +125,72 @@ def synth_patterns(b, h_img, w_img, gt, device, seed):
     pl = (torch.rand(b, 1, h_img + pad, w_img, device=device, generator=g) < 0.25).float()
     pr = warp_ops.apply_disparity_cu(pl.contiguous(), (-gt).round().int().contiguous())  # left -> right: x - d
     return pl.contiguous(), pr.contiguous()
+
+
+DUMP_BUDGET = (60 << 20) // 4  # float32 elements written by --dump-outputs, all arrays together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 .npy per array.  When they would exceed DUMP_BUDGET together, the smaller arrays
+    are written whole and each larger one as a fixed sample of its flattened elements (ascending indices drawn by a
+    generator seeded from the array's name), so that two runs with the same arguments write the same elements."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BUDGET
+    for i, (name, t) in enumerate(items):
+        t = t.detach().float()
+        cap = left // (len(items) - i)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randperm(t.numel(), generator=g)[:cap].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.cpu().numpy()
+        left -= arr.size
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def step_arrays(loss, outputs, module):
+    """What one training step computed: the loss, the outputs (name -> the tensors in the order the model returns
+    them: <name>0, <name>1, ...) and the gradients the optimizer step applied (flattened in parameters() order).
+    The updated parameters are not written: Adam's first step moves each one by lr * g / (|g| + eps), which turns the
+    rounding-level differences of a gradient near zero (float-atomic summation order) into differences of up to lr."""
+    params = list(module.parameters())
+    out = {"loss": loss.detach().reshape(1),
+           "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                               for p in params])}
+    for name, ts in outputs.items():
+        out.update({f"{name}{k}": t for k, t in enumerate(ts)})
+    return out
+
+
+class InitialState:
+    """Makes every warm-up and timed step the SAME training step: restore() puts the parameters, the buffers (BatchNorm
+    running statistics) and the Adam moments and step counts back where they were before the first step.  Steps that
+    carried on training would each start from the previous one's result, and the float-atomic summation order of the
+    gradients, amplified by Adam step after step, would make the last step's inputs and outputs differ from run to run
+    (two runs of 25 steps: gradients 86 % apart).  Cost: a few multi-tensor launches per step (21 MB copied, 42 MB of
+    moments zeroed)."""
+
+    def __init__(self, module, opt):
+        self.opt = opt
+        self.live = list(module.parameters()) + list(module.buffers())
+        self.init = [t.detach().clone() for t in self.live]
+        self.moments = self.counts = None
+
+    def restore(self):
+        with torch.no_grad():
+            torch._foreach_copy_(self.live, self.init)
+            if self.opt.state and self.moments is None:  # (Adam creates its state in its first step)
+                st = [self.opt.state[p] for g in self.opt.param_groups for p in g["params"] if p in self.opt.state]
+                self.moments = [s[k] for s in st for k in ("exp_avg", "exp_avg_sq")]
+                self.counts = [s["step"] for s in st]
+            if self.moments is not None:
+                torch._foreach_zero_(self.moments)
+                torch._foreach_zero_(self.counts)
 
 
 class heartbeat:
@@ -193,6 +273,20 @@ MIOPEN_DB_DIR = os.path.join(REPO, "profiles", "miopen_db")
 
 def _have_miopen_db():
     return os.path.isdir(MIOPEN_DB_DIR) and any(f.endswith(".txt") or f.endswith(".db") for f in os.listdir(MIOPEN_DB_DIR))
+
+
+def _miopen_db_copy():
+    """a private copy of the committed find-db, removed at exit: MIOpen rewrites the db it is given, and a run must leave
+    the committed files as they are (a --eager-tuned run, which is there to refresh them, writes the committed db itself)"""
+    import atexit
+    import shutil
+    import tempfile
+
+    tmp = tempfile.mkdtemp(prefix="az_miopen_db_")
+    atexit.register(shutil.rmtree, tmp, True)
+    for f in os.listdir(MIOPEN_DB_DIR):
+        shutil.copy2(os.path.join(MIOPEN_DB_DIR, f), tmp)
+    return tmp
 
 
 def _eager_mode(args):
@@ -408,7 +502,10 @@ def raft_workload(args, rank, local_rank, world):
     ys = torch.arange(h, device=device, dtype=torch.float32).view(1, 1, h, 1).expand(b, 1, h, w)
     coords0 = torch.cat([xs, ys], 1).contiguous()
 
+    fresh = InitialState(gru, opt)
+
     def step():
+        fresh.restore()
         opt.zero_grad(set_to_none=True)
         f1.grad = f2.grad = None
         corr_fn = CorrBlock1D(f1, f2, radius=4, num_levels=4)
@@ -422,19 +519,24 @@ def raft_workload(args, rank, local_rank, world):
             coords = torch.cat([coords[:, :1] + delta, coords[:, 1:]], 1)  # stereo: x only
         loss.backward()
         opt.step()
-        return loss
+        return loss, state
 
     for _ in range(args.warmup):
         step()
     azdist.fence()
-    profiler.start()
+    if args.full:
+        profiler.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        res = None  # (a step's outputs are not kept alive through the next one)
+        res = step()
     azdist.fence()
     dt = time.perf_counter() - t0
-    prof = profiler.stop()
+    prof = profiler.stop() if args.full else {}
     dt = azdist.max_over_ranks(dt, device)
+    loss, state = res
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_arrays(loss, {"state": [state], "fmap_grad": [f1.grad, f2.grad]}, gru))
     if rank == 0:
         vol = prof.get("corr1d_volume")
         roof = None
@@ -486,21 +588,27 @@ def dry_run(args, rank, world):
     x = torch.randn(args.batch, 2, 6, 8, 12, generator=g)
     y = torch.randn(args.batch, 1, 6, 8, 12, generator=g)
 
+    fresh = InitialState(model, opt)
+
     def step():
+        fresh.restore()
         opt.zero_grad(set_to_none=True)
-        loss = ((net(x) - y) ** 2).mean()
+        pred = net(x)
+        loss = ((pred - y) ** 2).mean()
         loss.backward()
         opt.step()
-        return loss
+        return loss, pred
 
     for _ in range(args.warmup):
         step()
     azdist.fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, pred = step()
     azdist.fence()
     dt = azdist.max_over_ranks(time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_arrays(loss, {"out": [pred]}, model))
     # every rank drew its own pairs and holds the same parameters after the all-reduced steps
     digest = torch.cat([p.detach().flatten() for p in model.parameters()]).double().sum()
     lo, hi = digest.clone(), digest.clone()
@@ -540,8 +648,10 @@ def main():
         return dry_run(args, rank, world)
     if args.workload == "raft":
         return raft_workload(args, rank, local_rank, world)
-    if _have_miopen_db() or args.eager_tuned:
+    if args.full and (_have_miopen_db() or args.eager_tuned):
         # (before anything initialises MIOpen; read by the eager legs only)
+        if _have_miopen_db() and not args.eager_tuned and "MIOPEN_USER_DB_PATH" not in os.environ:
+            os.environ["MIOPEN_USER_DB_PATH"] = _miopen_db_copy()
         os.environ.setdefault("MIOPEN_USER_DB_PATH", MIOPEN_DB_DIR if _have_miopen_db() else os.path.join(REPO, "gpurun_out", "miopen_db"))
         os.makedirs(os.environ["MIOPEN_USER_DB_PATH"], exist_ok=True)
         if not args.eager_tuned and os.environ.get("AZ_BENCH_EAGER_UNTUNED") != "1":
@@ -578,13 +688,17 @@ def main():
     seed = azdist.rank_seed(1234, rank)
     il, ir, gt = synth_batch(args.batch, args.height, args.width, args.maxdisp, device, seed)
 
+    fresh = InitialState(model, opt)
+
     if not mixed:
         def step():
+            fresh.restore()
             opt.zero_grad(set_to_none=True)
-            loss = disp_loss(net(il, ir), gt, args.maxdisp)
+            preds = net(il, ir)
+            loss = disp_loss(preds, gt, args.maxdisp)
             loss.backward()
             opt.step()
-            return loss
+            return loss, {"out": preds}
     else:
         # default.yaml iteration (train.py:220-432, utils/losses.py:81-156): ADAPTER=True -> 6-channel PSMNet
         # (the adapter itself is outside the path: its outputs are synthetic tanh(randn) images);
@@ -600,10 +714,11 @@ def main():
         ps = 11  # configs/config.py:41
 
         def step():
+            fresh.restore()
             opt.zero_grad(set_to_none=True)
-            out = net(il, ir, tl, tr)
-            loss = disp_loss(out, gt, args.maxdisp)
-            loss = loss + reprojection.get_reproj_error_patch(spl, spr, out[0], mask, ps)[0]
+            sim = net(il, ir, tl, tr)
+            loss = disp_loss(sim, gt, args.maxdisp)
+            loss = loss + reprojection.get_reproj_error_patch(spl, spr, sim[0], mask, ps)[0]
             loss.backward()
             opt.step()
             opt.zero_grad(set_to_none=True)
@@ -611,7 +726,7 @@ def main():
             real = reprojection.get_reproj_error_patch(rpl, rpr, out[0], None, ps)[0]
             real.backward()
             opt.step()
-            return loss + real.detach()
+            return loss + real.detach(), {"sim_out": sim, "real_out": out}
 
     fence = azdist.fence
 
@@ -630,16 +745,23 @@ def main():
             step()
     fence()
     note(f"timing {args.steps} steps")
-    profiler.start()  # HIP events around the dominant kernel, on the launch stream
+    if args.full:
+        profiler.start()  # HIP events around the dominant kernel, on the launch stream
     mem0 = torch.cuda.memory_stats(device)
     t0 = time.perf_counter()
     with on_stream():
         for _ in range(args.steps):
-            loss = step()
+            res = None  # (a step's outputs are not kept alive through the next one)
+            res = step()
     fence()
     dt = time.perf_counter() - t0
-    prof = profiler.stop()
+    prof = profiler.stop() if args.full else None
     dt = azdist.max_over_ranks(dt, device)
+    mem1 = torch.cuda.memory_stats(device)  # (taken before --dump-outputs allocates anything)
+    peak = torch.cuda.max_memory_allocated(device), torch.cuda.max_memory_reserved(device)
+    loss, outputs = res
+    if rank == 0 and args.dump_outputs:  # (before the eager legs of --full train the same model further)
+        dump_outputs(args.dump_outputs, step_arrays(loss, outputs, model))
 
     if rank == 0:
         pairs_per_step = args.batch * (2 if mixed else 1)  # mixed: one sim pair + one real pair per sample slot
@@ -673,15 +795,16 @@ def main():
                                      "bf16x6 = exact 3-way bf16 split, six MFMAs per product), fp32 accumulation "
                                      "everywhere; every convolution on this library's kernels"},
             "loss": float(loss.item()),
-            "peak_mem_gb": torch.cuda.max_memory_allocated(device) / 2 ** 30,
-            "peak_reserved_gb": torch.cuda.max_memory_reserved(device) / 2 ** 30,
+            "peak_mem_gb": peak[0] / 2 ** 30,
+            "peak_reserved_gb": peak[1] / 2 ** 30,
             # hipMalloc / hipFree calls of the caching allocator INSIDE the timed steps (a steady state has none)
-            "allocator_in_timed_steps": {k: int(torch.cuda.memory_stats(device).get(k, 0) - mem0.get(k, 0))
+            "allocator_in_timed_steps": {k: int(mem1.get(k, 0) - mem0.get(k, 0))
                                          for k in ("num_device_alloc", "num_device_free", "num_alloc_retries")},
             "roofline": profiler.roofline(prof, os.path.join(REPO, "profiles", "r05_pmc_traffic_b4.json"),
                                           os.path.join(REPO, "profiles", "r05_pmc_clock_b4.json"),
                                           ms_per_step=1e3 * dt / args.steps, steps=args.steps,
-                                          solo=solo_probe(args, device) if (world == 1 and not mixed and not args.no_solo_probe) else None),
+                                          solo=solo_probe(args, device) if (world == 1 and not mixed and not args.no_solo_probe) else None)
+                        if args.full else None,
             "cpu_baseline": None,
             "eager_gpu": None,
             "eager_stage": None,
@@ -694,7 +817,7 @@ def main():
             detail["measured_hbm"] = hbm_probe(device)
             rf["measured_hbm_gbps"] = detail["measured_hbm"]["GB/s"]
             rf["detail"] = detail
-        if world == 1 and not mixed and args.eager_steps > 0:
+        if args.full and world == 1 and not mixed and args.eager_steps > 0:
             note(f"{1e3 * dt / args.steps:.1f} ms/step; timing the PyTorch-eager step on the GPU")
             del opt
             if not args.no_stage_bench:
@@ -718,7 +841,7 @@ def main():
                            "this_library_pairs_per_s": out["value"], "command": " ".join(sys.argv)},
                           open(os.path.join(REPO, "gpurun_out", "r04_eager_tuned.json")
                                if os.path.isdir(os.path.join(REPO, "gpurun_out")) else TUNED_EAGER_JSON, "w"), indent=1)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             note("timing the CPU baseline samples")
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)

@@ -44,3 +44,63 @@ def test_bench_refuses_a_world_size_that_does_not_match_gpus():
                        capture_output=True, text=True, cwd=REPO, env={k: v for k, v in os.environ.items()
                                                                       if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def _dry_run_dump(path, steps=2, warmup=1):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warmup), "--dry-run", "--dist-backend", "gloo", "--dump-outputs", str(path)],
+                       capture_output=True, text=True, cwd=REPO, env=dict(env, OMP_NUM_THREADS="1"), timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == steps and out["warmup"] == warmup and out["ms_per_step"] > 0
+    return out
+
+
+def test_bench_dump_outputs_are_float32_and_repeatable(tmp_path):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files, the same from run to run"""
+    import numpy as np
+
+    a, b = _dry_run_dump(tmp_path / "a"), _dry_run_dump(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "grads.npy", "out0.npy"} <= set(names)
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all(), n
+        np.testing.assert_array_equal(x, y, err_msg=n)
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == np.float32(a["loss"])
+    assert a["loss"] == b["loss"]
+
+
+def test_bench_steps_all_start_from_the_initial_state(tmp_path):
+    """every warm-up and timed step is the same training step from the same model and optimizer state: the last of
+    five steps computes exactly what a single step does"""
+    import numpy as np
+
+    one, five = _dry_run_dump(tmp_path / "one", 1, 0), _dry_run_dump(tmp_path / "five", 3, 2)
+    assert one["loss"] == five["loss"]
+    for n in sorted(os.listdir(tmp_path / "one")):
+        np.testing.assert_array_equal(np.load(tmp_path / "one" / n), np.load(tmp_path / "five" / n), err_msg=n)
+
+
+def test_dump_outputs_samples_within_the_budget(tmp_path, monkeypatch):
+    """arrays over the budget are written as a fixed sample of their elements; the small ones whole"""
+    import numpy as np
+    import torch
+
+    monkeypatch.syspath_prepend(REPO)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1000)
+    arrays = {"small": torch.arange(10.0), "big": torch.arange(5000.0).reshape(50, 100),
+              "bigger": torch.arange(8000, dtype=torch.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    small, big, bigger = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "big", "bigger"))
+    assert small.dtype == big.dtype == bigger.dtype == np.float32
+    np.testing.assert_array_equal(small, np.arange(10.0))
+    assert big.size + bigger.size + small.size <= 1000 and big.size == 495 and bigger.size == 495
+    assert (np.diff(big) > 0).all() and set(big) <= set(np.arange(5000.0))  # ascending picks of the flat elements
+    for n in ("big", "bigger"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy"))

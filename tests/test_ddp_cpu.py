@@ -28,6 +28,7 @@ def _batch(seed):
 
 
 def _worker(rank, world, port, out):
+    torch.set_num_threads(1)  # (the same CPU kernels as _expectation's, whatever the machine)
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
                       MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from activezero_amd import dist as azdist
@@ -48,6 +49,21 @@ def _worker(rank, world, port, out):
     azdist.shutdown()
 
 
+def _expectation(world, out):
+    """DDP averages the per-rank gradients; BatchNorm statistics stay per-rank (no SyncBN), so the expectation is the
+    mean of two independent single-rank backward passes -- computed in a fresh process like the ranks, so that nothing
+    an earlier test did to this one's torch state enters the comparison"""
+    torch.set_num_threads(1)
+    expect = None
+    for rank in range(world):
+        m = _tiny()
+        x, y = _batch(1234 + rank)
+        ((m(x) - y) ** 2).mean().backward()
+        gs = [p.grad for p in m.parameters()]
+        expect = gs if expect is None else [a + b for a, b in zip(expect, gs)]
+    out.put([(g / world).numpy().copy() for g in expect])
+
+
 @pytest.mark.timeout(300)
 def test_ddp_two_ranks_gloo_matches_single_process_average():
     world, port = 2, _free_port()
@@ -64,16 +80,11 @@ def test_ddp_two_ranks_gloo_matches_single_process_average():
     # every rank sees the max step time; ranks drew different pairs
     assert t0 == t1 == 2.0
     assert not (x0 == x1).all()
-    # DDP averages the per-rank gradients; BatchNorm statistics stay per-rank (no SyncBN),
-    # so the expectation is the mean of two independent single-rank backward passes
-    expect = None
-    for rank in range(world):
-        m = _tiny()
-        x, y = _batch(1234 + rank)
-        ((m(x) - y) ** 2).mean().backward()
-        gs = [p.grad for p in m.parameters()]
-        expect = gs if expect is None else [a + b for a, b in zip(expect, gs)]
-    expect = [g / world for g in expect]
+    ref = ctx.Process(target=_expectation, args=(world, out))
+    ref.start()
+    expect = [torch.from_numpy(g) for g in out.get(timeout=240)]
+    ref.join(60)
+    assert ref.exitcode == 0
     for a, b, e in zip(g0, g1, expect):
         assert (a == b).all()
         assert torch.allclose(torch.from_numpy(a), e, rtol=1e-5, atol=1e-7)

@@ -5,8 +5,8 @@
    the build while `nets.adapter`, `nets.dispnet`, `utils.losses` ... keep resolving from the reference
    tree (pkgutil.extend_path in activezero_amd/{nets,utils}/__init__.py).  The reference checkout itself is
    not available on the GPU box, so the test builds a throw-away tree with the reference's package layout
-   (empty modules of the same names); when /root/reference exists (the build container) the real tree is
-   checked as well, by FILE LOCATION only -- nothing of it is imported or executed.
+   (empty modules of the same names), once with a minimal layout and once with the reference checkout's own
+   (tests/golden/reference_layout.json), by FILE LOCATION only -- nothing of it is imported or executed.
 2. The argument checks of the 2-D convolution C ABI run on the host (no GPU needed).
 3. The oracle reproduces the reference's D = 192 golden (tools/make_goldens.py g11)."""
 import ctypes
@@ -65,9 +65,18 @@ def test_overlay_resolution_on_a_reference_shaped_tree(tmp_path):
     _check(_resolve(str(ref)), str(ref))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/nets"), reason="reference checkout only exists in the build container")
-def test_overlay_resolution_on_the_reference_checkout():
-    _check(_resolve("/root/reference"), "/root/reference")
+def test_overlay_resolution_on_the_reference_checkout(tmp_path):
+    """the reference checkout's own package layout, recorded in tests/golden/reference_layout.json (file names only:
+    no __init__.py in nets/psmnet, nets/dispnet, nets/raft), rebuilt as empty modules"""
+    import json
+
+    layout = json.load(open(os.path.join(REPO, "tests", "golden", "reference_layout.json")))["files"]
+    ref = tmp_path / "ActiveZero"
+    for rel in layout:
+        f = ref / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text("# stand-in with the reference's module name\n")
+    _check(_resolve(str(ref)), str(ref))
 
 
 def test_conv2d_abi_argument_validation_on_host():

@@ -5,7 +5,7 @@ import json, subprocess, sys, os
 n = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 30
 extra = [a for a in sys.argv[1:] if not a.isdigit()]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
+r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
                     "--eager-steps", "0", "--no-stage-bench"] + extra, capture_output=True, text=True)
 d = json.loads(r.stdout.strip().splitlines()[-1])
 print("%.2f ms/step  %.2f pairs/s  loss %.5f  peak %.1f GB" % (d["ms_per_step"], d["value"], d["loss"], d["peak_mem_gb"]))

@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $out/trace -o t --output-format csv -- python3 $root/bench.py --steps 1 --warmup 1 --no-cpu-baseline --eager-steps 0 --no-stage-bench "$@" > $out/trace_bench.log 2>&1
+rocprofv3 --kernel-trace -d $out/trace -o t --output-format csv -- python3 $root/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --eager-steps 0 --no-stage-bench "$@" > $out/trace_bench.log 2>&1
 python3 - <<PY
 import csv, glob
 names = set()
