@@ -1,0 +1,443 @@
+"""GPU: the stride-1 3x3x3 layers -- forward, input gradient and weight gradient -- against fp64, element-wise, on every route
+a layer of this family can take: the depth-rolling kernel with 32 output channels and its two-workgroup 64 -> 64 form
+(az_conv3d_roll.hip), the f16x3 gather kernel (az_conv3d.hip), the bf16x6 m128 kernel (az_conv3d_m128.hip, behind
+AZ_CONV_ROLL=0), the weight gradient of az_conv3d_wgrad16.hip at AR 0 (bf16x6) and AR 1 (f16x3) with pre-split operands
+(split masks 0-3), its wide form, its persistent column walk and XCD column map, the one-kd-per-wave kernels of
+az_conv3d_wgrad.hip (fp32; bf16x6 behind AZ_WGRAD_R16=0), and the accumulate-only launch + az_wgrad_unpack_multi.
+
+Each case asserts the route it takes before it launches and runs the checks of tests/_fp64ref.py: (a) the worst-case bound
+against the exact result, (b) and (c) random-walk bounds against the exact value of the products the arithmetic forms; it
+prints the three ratios (<= 1 passes), and the module prints the largest of each per arithmetic and kind.
+tests/test_conv_error_model_cpu.py shows that the checks reject the defects they are meant to see.  tests/test_gpu_switches.py
+runs this file again behind the switches that change its routes."""
+import functools
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from activezero_amd import _lib, conv3d, overlap  # noqa: E402
+from activezero_amd.ops import _call, _p, _stream  # noqa: E402
+from tests import _fp64ref as R  # noqa: E402
+from tests._weights import seeded  # noqa: E402
+
+DEV = torch.device("cuda:0")
+PAIRS = [(32, 32), (32, 64), (64, 32), (64, 64)]
+SMALL = [(1, 1, 1, 1), (1, 1, 3, 3), (1, 5, 7, 19), (2, 4, 9, 16), (1, 3, 2, 15), (3, 2, 5, 33), (1, 13, 25, 17)]
+# above the column-walk threshold of the weight gradient's tile count (slots = 512 / ntiles in az_conv3d_wgrad_r16_launch):
+# ncols = B D ceil(W / 16) = 528 > 512 (32 x 32), 272 > 256 (32 x 64, 64 x 32), 136 > 128 (64 x 64)
+WALK = {(32, 32): (1, 24, 5, 352), (32, 64): (1, 16, 3, 272), (64, 32): (1, 16, 3, 272), (64, 64): (1, 8, 3, 272)}
+PREC = {"f16x3": conv3d.F16X3, "bf16x6": conv3d.BF16X6, "fp32": conv3d.FP32}
+LAYOUT_GATHER, LAYOUT_ROLL, LAYOUT_ROLL2 = 2, 3, 4  # include/azhip.h AZ_PACK_3D_*
+WORST = {}  # (arith, kind) -> [max ratio a, b, c] over the cases run
+
+
+def lib():
+    return _lib.lib()
+
+
+def opt(name):
+    return lib().az_option(name.encode())
+
+
+def cl(x):
+    return x.permute(0, 2, 3, 4, 1).contiguous().to(DEV)
+
+
+def ncdhw(x):
+    return x.detach().permute(0, 4, 1, 2, 3)
+
+
+def r16_workgroups(ncols, slots, ntiles, cap):
+    """az_launch_math.h az_wgrad16_workgroups (persistent workgroups per tile of the r16 weight gradient)"""
+    best, best_score = 1, -1.0
+    step = 8 // (4 if ntiles > 2 else ntiles)
+    w = slots
+    while w >= slots // 4 and w >= 1:
+        if w <= ncols:
+            per = (ncols + w - 1) // w
+            score = ncols / (per * slots)
+            if score > best_score + 1e-9:
+                best_score, best = score, w
+        w -= step
+    if ncols < slots // 4:
+        best = max(ncols, 1)
+    if 0 < cap < best:
+        best = cap
+    return best
+
+
+def route(kind, cin, cout, arith, shape, split_mask=0):
+    """the kernel this call takes, asserted against the library's and the wrapper's own routing answers"""
+    b, d, h, w = shape
+    x = torch.empty(b, d, h, w, max(cin, cout), device="meta")
+    assert conv3d._fits32(x, cin, cout)  # (no flat-address fallback at these sizes)
+    if kind in ("fwd", "dgrad"):
+        ci, co = (cin, cout) if kind == "fwd" else (cout, cin)  # the launch's channels (an input gradient is a forward of dy)
+        if arith == "f16x3":
+            assert conv3d._f16_fwd_ok(conv3d.CONV_S1, ci, co)
+            lay = lib().az_conv3d_f16_layout(conv3d.CONV_S1, ci, co)
+            want = LAYOUT_ROLL2 if (ci == co == 64 and opt("AZ_CONV_ROLL64")) else (LAYOUT_ROLL if co == 32 else LAYOUT_GATHER)
+            assert lay == want, (lay, want)
+            name = {LAYOUT_ROLL: "roll", LAYOUT_ROLL2: "roll2", LAYOUT_GATHER: "gather"}[lay] + " f16x3"
+            if split_mask:
+                assert lib().az_conv3d_fwd_f16_split_ok(conv3d.CONV_S1, b, ci, co, d, h, w) == 1
+                name += " presplit"
+            return name
+        prec = PREC[arith]
+        lay = conv3d._layout(prec, conv3d.CONV_S1, co)
+        if arith == "bf16x6" and co == 32 and conv3d._ROLL:
+            assert lay == conv3d.BF16X6_R16
+            return "roll bf16x6"
+        assert lay == prec
+        if arith == "bf16x6" and co == 32 and opt("AZ_CONV_M128"):
+            return "m128 bf16x6"
+        return f"gather {arith}"
+    cm, cn = cout, cin  # coarse = dy, fine = x
+    ntiles = (cm // 32) * (cn // 32)
+    r16 = opt("AZ_WGRAD_R16")
+    if arith == "f16x3" or (arith == "bf16x6" and (r16 >= 2 or (r16 == 1 and cm == cn == 32))):
+        if arith == "f16x3":
+            assert conv3d._f16_wgrad_ok(conv3d.CONV_S1, cin, cout)
+            assert lib().az_conv3d_wgrad_f16_split_ok(1, b, cm, cn, d, h, w, d, h, w) == 3  # (= the r16 kernel takes it)
+            name = "r16 AR1" + (" wide" if opt("AZ_WGRAD_R16_WIDE") else "") + f" mask {split_mask}"
+        else:
+            assert split_mask == 0
+            name = "r16 AR0"
+        ncols = b * d * ((w + 15) // 16)
+        wgs = r16_workgroups(ncols, 512 // ntiles, ntiles, opt("AZ_WGRAD_R16_WGS"))
+        if ncols > wgs:
+            name += " walk"
+        if opt("AZ_WGRAD_R16_XCD") and wgs % 8 == 0:
+            name += " xcd"
+        return name
+    assert split_mask == 0
+    if arith == "bf16x6":
+        return "one-kd bf16x6" + (" fw" if opt("AZ_WGRAD_FW") else "")
+    return "one-kd fp32"
+
+
+def test_every_route_of_the_family_is_swept():
+    """the cases of this file together take every route the current switches leave to this family"""
+    names = {route(k, ci, co, a, s) for (ci, co, s, k, a) in CASES}
+    names |= {route("wgrad", ci, co, "f16x3", s, m) for (ci, co, s, m) in PRESPLIT_WGRAD}
+    names |= {route("dgrad", ci, co, "f16x3", s, 1) for (ci, co, s) in PRESPLIT_DGRAD
+              if lib().az_conv3d_fwd_f16_split_ok(conv3d.CONV_S1, s[0], co, ci, *s[1:]) == 1}
+    want = ["roll f16x3", "gather f16x3", "gather fp32", "one-kd fp32", "r16 AR1", "walk", "roll f16x3 presplit"]
+    want += ["roll2 f16x3", "roll2 f16x3 presplit"] if opt("AZ_CONV_ROLL64") else []
+    want += [f"mask {m}" for m in range(4)]
+    want += ["roll bf16x6" if conv3d._ROLL else ("m128 bf16x6" if opt("AZ_CONV_M128") else "gather bf16x6"), "gather bf16x6"]
+    want += ["r16 AR0"] if opt("AZ_WGRAD_R16") else ["one-kd bf16x6" + (" fw" if opt("AZ_WGRAD_FW") else "")]
+    want += ["xcd"] if opt("AZ_WGRAD_R16_XCD") and opt("AZ_WGRAD_R16_WGS") % 8 == 0 else []
+    want += ["wide"] if opt("AZ_WGRAD_R16_WIDE") else []
+    missing = [n for n in want if not any(n in r for r in names)]
+    assert not missing, (missing, sorted(names))
+
+
+def run(kind, cin, cout, arith, x, wt, dy, residual=None):
+    """x, wt, dy on the GPU (channels-last volumes); the result in NCDHW / weight layout"""
+    prec = PREC[arith]
+    with torch.no_grad():
+        if kind == "fwd":
+            return ncdhw(conv3d._conv(x, wt, conv3d.CONV_S1, prec))
+        if kind == "dgrad":
+            return ncdhw(conv3d._input_grad(dy, wt, conv3d.CONV_S1, cin, cout, prec, residual=residual))
+        return conv3d._weight_grad(x, dy, conv3d.CONV_S1, cin, cout, prec)
+
+
+@functools.lru_cache(maxsize=16)
+def operands(cin, cout, shape):
+    b, d, h, w = shape
+    seed = 7300 + 97 * (cin // 32) + 13 * (cout // 32) + 7 * b + 5 * d + 3 * h + w
+    x = seeded((b, cin, d, h, w), seed)
+    wt = seeded((cout, cin, 3, 3, 3), seed + 1, -0.2, 0.2)
+    dy = seeded((b, cout, d, h, w), seed + 2) * 1e-3
+    return x, wt, dy
+
+
+def pq(kind, x, wt, dy):
+    return {"fwd": (x, wt), "dgrad": (dy, wt), "wgrad": (x, dy)}[kind]
+
+
+@functools.lru_cache(maxsize=16)
+def reference(kind, cin, cout, shape):
+    """fp64 result and magnitude sums, shared by the three arithmetics (large shapes: fp64 GEMMs on the GPU)"""
+    p, q = pq(kind, *operands(cin, cout, shape))
+    gemm = shape in WALK.values()
+    if gemm:
+        p, q = p.to(DEV), q.to(DEV)
+    return R.exact(kind, p, q, gemm=gemm)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def worst_ratios(request):
+    """at the end of the module: the largest ratio of each check per arithmetic and kind over the cases this run executed"""
+    yield
+    capman = request.config.pluginmanager.getplugin("capturemanager")
+    if capman is not None and WORST:
+        with capman.global_and_fixture_disabled():
+            print("\nworst err / bound per arithmetic and kind:  check (a)  check (b)  check (c)")
+            for (a, k), r in sorted(WORST.items()):
+                print(f"  {a:7s} {k:6s}  " + "  ".join(f"{v:9.4f}" for v in r))
+
+
+def record(arith, kind, label, r, capsys):
+    w = WORST.setdefault((arith, kind), [0.0, 0.0, 0.0])
+    w[:] = [max(u, v) for u, v in zip(w, r)]
+    with capsys.disabled():
+        print(f"\n{label}: (a) {r[0]:.4f} (b) {r[1]:.4f} (c) {r[2]:.4f}")
+
+
+CASES = [(ci, co, s, k, a) for (ci, co) in PAIRS for s in SMALL + [WALK[(ci, co)]] for k in R.KINDS for a in R.ARITHS]
+
+
+@pytest.mark.parametrize("cin,cout,shape,kind,arith", CASES,
+                         ids=[f"{k}-{ci}x{co}-{'x'.join(map(str, s))}-{a}" for (ci, co, s, k, a) in CASES])
+def test_stride1_vs_fp64(cin, cout, shape, kind, arith, capsys):
+    x, wt, dy = operands(cin, cout, shape)
+    p, q = pq(kind, x, wt, dy)
+    name = route(kind, cin, cout, arith, shape)
+    got = run(kind, cin, cout, arith, cl(x), wt.to(DEV), cl(dy))
+    ex = reference(kind, cin, cout, shape)
+    gemm = shape in WALK.values()
+    dev = DEV if gemm else "cpu"
+    sref = R.split_reference(kind, p.to(dev), q.to(dev), arith, gemm=gemm)
+    r = R.check(got, arith, R.products(kind, p, q), ex, sref, R.amax_of(p), R.amax_of(q))
+    record(arith, kind, f"{kind} {cin}->{cout} {shape} {arith} [{name}]", r, capsys)
+    assert max(r) <= 1.0, (name, r)
+
+
+RESIDUAL = [(ci, co, s, a) for (ci, co) in PAIRS for s in [(1, 5, 7, 19), (3, 2, 5, 33)] for a in R.ARITHS]
+
+
+@pytest.mark.parametrize("cin,cout,shape,arith", RESIDUAL,
+                         ids=[f"{ci}x{co}-{'x'.join(map(str, s))}-{a}" for (ci, co, s, a) in RESIDUAL])
+def test_dgrad_residual_handover(cin, cout, shape, arith, capsys):
+    """the gradient hand-over epilogue: dx = conv_transpose(dy) + residual, added in the input-gradient kernel"""
+    x, wt, dy = operands(cin, cout, shape)
+    b, d, h, w = shape
+    res = seeded((b, cin, d, h, w), 7400) * 1e-2
+    name = route("dgrad", cin, cout, arith, shape)
+    got = run("dgrad", cin, cout, arith, None, wt.to(DEV), cl(dy), residual=cl(res))
+    ex = reference("dgrad", cin, cout, shape)
+    sref = R.split_reference("dgrad", dy, wt, arith)
+    r = R.check(got, arith, R.products("dgrad", dy, wt), ex, sref, R.amax_of(dy), R.amax_of(wt), addend=res)
+    record(arith, "dgrad", f"dgrad+residual {cin}->{cout} {shape} {arith} [{name}]", r, capsys)
+    assert max(r) <= 1.0, (name, r)
+
+
+# ---- pre-split operands (include/azhip.h "S2 format") ------------------------------------------------------------------------
+def presplit(t_cl, seed):
+    """t -> (the pre-split tensor az_bn3d_bwd(split_out = 1) writes for an identity BatchNorm, the same values as floats
+    from a second launch) -- as tests/test_gpu_s2roll.py builds it"""
+    c = t_cl.shape[-1]
+    nv = t_cl.numel() // c
+    raw = cl(seeded((t_cl.shape[0], c) + tuple(t_cl.shape[1:4]), seed))
+    wsb = lib().az_bn3d_bwd_workspace(nv, c)
+    v = [torch.zeros(c, device=DEV), torch.ones(c, device=DEV), torch.ones(c, device=DEV)]
+    outs = []
+    for split in (1, 0):
+        ws, dx = torch.empty(wsb // 4, device=DEV), torch.empty_like(t_cl)
+        small = [torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty(c, 3, device=DEV)]
+        am = torch.zeros(conv3d.AMAX_SLOTS, device=DEV)
+        _call("az_bn3d_bwd", _p(dx), None, _p(small[0]), _p(small[1]), _p(small[2]), _p(ws), wsb, _p(t_cl), None, _p(raw),
+              _p(v[0]), _p(v[1]), _p(v[2]), None, None, 0, nv, c, _p(am), split, _stream())
+        if split:
+            conv3d._set_amax(dx, am)
+            dx.az_split = True
+        outs.append(dx)
+    return outs
+
+
+def decoded_parts(t):
+    """a pre-split tensor -> its [hi, lo] parts (NCDHW fp64, unscaled) and the amax bound they were scaled by"""
+    a = float(conv3d._get_amax(t)[::64].max())
+    k = R.f16_scale_exp(a)
+    f = t.contiguous().view(torch.int16).view(-1, 8).view(torch.float16).double().cpu()
+    hi, lo = (f[:, :4].reshape(t.shape), f[:, 4:].reshape(t.shape))
+    return [ncdhw(hi).cpu() * 2.0 ** -k, ncdhw(lo).cpu() * 2.0 ** -k], a
+
+
+def _split_operand(t_cl, seed):
+    split, plain = presplit(t_cl, seed)
+    parts, bound = decoded_parts(split)
+    vals = ncdhw(plain).cpu().double()
+    # the stored parts are the split of the float values (up to the operand's 2^-22 and the subnormal spacing of lo)
+    assert float((parts[0] + parts[1] - vals).abs().max()) <= 2.0 ** -22 * float(vals.abs().max()) + 2.0 ** -39 * bound
+    return split, plain, parts, bound
+
+
+PRESPLIT_WGRAD = [(ci, co, s, m) for (ci, co) in PAIRS for s in [(1, 5, 7, 19), (2, 4, 9, 16), (3, 2, 5, 33), WALK[(ci, co)]]
+                  for m in (1, 2, 3)]
+
+
+@pytest.mark.parametrize("cin,cout,shape,mask", PRESPLIT_WGRAD,
+                         ids=[f"{ci}x{co}-{'x'.join(map(str, s))}-mask{m}" for (ci, co, s, m) in PRESPLIT_WGRAD])
+def test_wgrad_presplit_operands_vs_fp64(cin, cout, shape, mask, capsys):
+    if not conv3d.PRESPLIT:
+        pytest.skip("AZ_PRESPLIT=0")
+    x, wt, dy = operands(cin, cout, shape)
+    xg, dg = cl(x), cl(dy)
+    parts_x = parts_dy = None
+    am_x, am_dy = R.amax_of(x), R.amax_of(dy)
+    if mask & 1:  # coarse = dy
+        dg, plain, parts_dy, am_dy = _split_operand(dg, 7410)
+        dy = ncdhw(plain).cpu()
+    if mask & 2:  # fine = x
+        xg, plain, parts_x, am_x = _split_operand(xg, 7420)
+        x = ncdhw(plain).cpu()
+    name = route("wgrad", cin, cout, "f16x3", shape, split_mask=mask)
+    with torch.no_grad():
+        got = conv3d._wgrad_f16(dg, xg, 1, cout, cin, "conv")
+    gemm = shape in WALK.values()
+    dev = DEV if gemm else "cpu"
+    mv = (lambda ps: None if ps is None else [t.to(dev) for t in ps])
+    ex = R.exact("wgrad", x.to(dev), dy.to(dev), gemm=gemm)
+    sref = R.split_reference("wgrad", x.to(dev), dy.to(dev), "f16x3", parts_p=mv(parts_x), parts_q=mv(parts_dy), gemm=gemm)
+    r = R.check(got, "f16x3", R.products("wgrad", x, dy), ex, sref, am_x, am_dy)
+    record("f16x3", "wgrad", f"wgrad presplit {cin}->{cout} {shape} [{name}]", r, capsys)
+    assert max(r) <= 1.0, (name, r)
+
+
+# (the pairs whose input-gradient launch stages a pre-split input: the depth-rolling kernels)
+PRESPLIT_DGRAD = [(ci, co, s) for (ci, co) in [(32, 32), (32, 64), (64, 64)]
+                  for s in [(1, 5, 7, 19), (2, 4, 9, 16), (1, 13, 25, 17)]]
+
+
+@pytest.mark.parametrize("cin,cout,shape", PRESPLIT_DGRAD,
+                         ids=[f"{ci}x{co}-{'x'.join(map(str, s))}" for (ci, co, s) in PRESPLIT_DGRAD])
+def test_dgrad_presplit_operand_vs_fp64(cin, cout, shape, capsys):
+    if not conv3d.PRESPLIT or (cin == cout == 64 and not opt("AZ_CONV_ROLL64")):
+        pytest.skip("AZ_PRESPLIT=0 / AZ_CONV_ROLL64=0: the launch reads floats only")
+    _, wt, dy = operands(cin, cout, shape)
+    split, plain, parts_dy, am_dy = _split_operand(cl(dy), 7430)
+    dy = ncdhw(plain).cpu()
+    name = route("dgrad", cin, cout, "f16x3", shape, split_mask=1)
+    with torch.no_grad():
+        got = ncdhw(conv3d._input_grad(split, wt.to(DEV), conv3d.CONV_S1, cin, cout, conv3d.F16X3))
+    ex = R.exact("dgrad", dy, wt)
+    sref = R.split_reference("dgrad", dy, wt, "f16x3", parts_p=parts_dy)
+    r = R.check(got, "f16x3", R.products("dgrad", dy, wt), ex, sref, am_dy, R.amax_of(wt))
+    record("f16x3", "dgrad", f"dgrad presplit {cin}->{cout} {shape} [{name}]", r, capsys)
+    assert max(r) <= 1.0, (name, r)
+
+
+# ---- accumulate-only weight gradients + one unpack of the pass (overlap.Sink) ------------------------------------------------
+def test_accumulate_only_into_one_arena_then_unpack(capsys):
+    layers = [(32, 64, (1, 5, 7, 19)), (64, 32, (2, 4, 9, 16)), (64, 64, (1, 3, 2, 15))]  # (cin, cout, shape)
+    sizes = [(lib().az_conv3d_wgrad_workspace(co, ci) // 4 + 63) & ~63 for (ci, co, _) in layers]
+    guard = 4096
+    arena = torch.zeros(sum(sizes) + guard, device=DEV)
+    sink = overlap.Sink(DEV)
+    grads, keep, off = [], [], 0
+    for (ci, co, shape), n in zip(layers, sizes):
+        b, d, h, w = shape
+        x, wt, dy = operands(ci, co, shape)
+        xg, dg = cl(x), cl(dy)
+        am_x, am_dy = conv3d.absmax(xg), conv3d.absmax(dg)
+        ws = arena[off:off + n]
+        off += n
+        gw = torch.full((co, ci, 3, 3, 3), float("nan"), device=DEV)
+        route("wgrad", ci, co, "f16x3", shape)
+        _call("az_conv3d_wgrad_f16", None, _p(ws), n * 4, _p(dg), _p(xg), _p(am_dy), _p(am_x), 0, 1, b, co, ci,
+              d, h, w, d, h, w, _stream())
+        sink.defer_unpack(gw, ws, co, ci, co, ci, 27)
+        grads.append(gw)
+        keep += [xg, dg, am_x, am_dy]
+    sink.stream.wait_stream(torch.cuda.current_stream())
+    sink._flush_pending()
+    torch.cuda.current_stream().wait_stream(sink.stream)
+    torch.cuda.synchronize()
+    assert float(arena[off:].abs().max()) == 0.0, "a launch wrote past its workspace"
+    for (ci, co, shape), gw in zip(layers, grads):
+        x, _, dy = operands(ci, co, shape)
+        ex = reference("wgrad", ci, co, shape)
+        sref = R.split_reference("wgrad", x, dy, "f16x3")
+        r = R.check(gw, "f16x3", R.products("wgrad", x, dy), ex, sref, R.amax_of(x), R.amax_of(dy))
+        record("f16x3", "wgrad", f"wgrad accumulate-only + unpack {ci}->{co} {shape}", r, capsys)
+        assert max(r) <= 1.0, (ci, co, shape, r)
+
+
+# ---- one full-size layer: B = 1 at V0, 32 -> 32, f16x3 ------------------------------------------------------------------------
+def _sample_points(b, d, h, w, n_random, seed):
+    """all outputs of the first and last depth plane, of the first and last row and column, and random voxels"""
+    ar = torch.arange
+    pts = []
+    for dd in (0, d - 1):
+        hh, ww = torch.meshgrid(ar(h), ar(w), indexing="ij")
+        pts.append(torch.stack([torch.zeros_like(hh), torch.full_like(hh, dd), hh, ww], -1).reshape(-1, 4))
+    for hh0 in (0, h - 1):
+        dd, ww = torch.meshgrid(ar(d), ar(w), indexing="ij")
+        pts.append(torch.stack([torch.zeros_like(dd), dd, torch.full_like(dd, hh0), ww], -1).reshape(-1, 4))
+    for ww0 in (0, w - 1):
+        dd, hh = torch.meshgrid(ar(d), ar(h), indexing="ij")
+        pts.append(torch.stack([torch.zeros_like(dd), dd, hh, torch.full_like(dd, ww0)], -1).reshape(-1, 4))
+    g = torch.Generator().manual_seed(seed)
+    pts.append(torch.stack([torch.randint(0, n, (n_random,), generator=g) for n in (b, d, h, w)], -1))
+    return torch.cat(pts).to(DEV)
+
+
+def _sampled_reference(p_cl, wt, pts, chunk=16384):
+    """fp64 y / S / Q2 / sum_q / sum_p / f16x3 split reference of a stride-1 forward at the voxels `pts`, each from its 27-tap
+    neighbourhood (p_cl: [B,D,H,W,C] on the GPU, wt: [cout,cin,3,3,3])"""
+    c, cout = p_cl.shape[-1], wt.shape[0]
+    offs = torch.tensor([[0, kd, kh, kw] for kd in range(3) for kh in range(3) for kw in range(3)], device=DEV)
+    wm = wt.double().to(DEV).permute(2, 3, 4, 1, 0).reshape(27 * c, cout)
+    hq, lq = [t.to(DEV).permute(2, 3, 4, 1, 0).reshape(27 * c, cout) for t in R.split_parts(wt, "f16x3")]
+    pad = lambda t: torch.nn.functional.pad(t, (0, 0, 1, 1, 1, 1, 1, 1))  # noqa: E731
+    hp, lp = [pad(t.permute(0, 2, 3, 4, 1)) for t in R.split_parts(p_cl.permute(0, 4, 1, 2, 3), "f16x3")]
+    xp = pad(p_cl.double())
+    ones = pad(torch.ones_like(p_cl, dtype=torch.float64))
+    keys = ("y", "S", "Q2", "sum_q", "sum_p", "sref")
+    out = {k: [] for k in keys}
+    for i in range(0, pts.shape[0], chunk):
+        idx = pts[i:i + chunk, None, :] + offs[None]
+        at = lambda t: t[idx[..., 0], idx[..., 1], idx[..., 2], idx[..., 3]].reshape(idx.shape[0], 27 * c)  # noqa: E731
+        nb, nh, nl = at(xp), at(hp), at(lp)
+        out["y"].append(nb @ wm)
+        out["S"].append(nb.abs() @ wm.abs())
+        out["Q2"].append((nb * nb) @ (wm * wm))
+        out["sum_q"].append(at(ones) @ wm.abs())
+        out["sum_p"].append(nb.abs().sum(1, keepdim=True).expand(-1, cout))
+        out["sref"].append(nh @ (hq + lq) + nl @ hq)
+    return {k: torch.cat(v) for k, v in out.items()}
+
+
+def test_full_size_v0_layer_f16x3(capsys):
+    """the XCD-mapped column walk of the weight gradient at its production size, element-wise against fp64 GEMMs; forward
+    and input gradient at sampled outputs"""
+    b, d, h, w, c = 1, 48, 136, 240, 32
+    g = torch.Generator(device=DEV).manual_seed(7500)
+    x = torch.rand(b, d, h, w, c, generator=g, device=DEV) * 2 - 1
+    dy = (torch.rand(b, d, h, w, c, generator=g, device=DEV) * 2 - 1) * 1e-3
+    wt = (torch.rand(c, c, 3, 3, 3, generator=g, device=DEV) * 0.4 - 0.2)
+    shape = (b, d, h, w)
+    for kind in R.KINDS:
+        name = route(kind, c, c, "f16x3", shape)
+        got = run(kind, c, c, "f16x3", x, wt, dy)
+        if kind == "wgrad":
+            assert "walk" in name and ("xcd" in name or not opt("AZ_WGRAD_R16_XCD")), name
+            p, q = ncdhw(x), ncdhw(dy)
+            ex = R.exact("wgrad", p, q, gemm=True)
+            sref = R.split_reference("wgrad", p, q, "f16x3", gemm=True)
+            r = R.check(got, "f16x3", b * d * h * w, ex, sref, R.amax_of(x), R.amax_of(dy))
+            # what one column of the walk (depth plane 17, positions 128 .. 143 of every row) contributes to each output: a
+            # column walked twice or skipped would move the result by that much; check (c) must see it at this size
+            col = torch.zeros_like(q)
+            col[:, :, 17, :, 128:144] = q[:, :, 17, :, 128:144]
+            one = R.op_gemm("wgrad", p, col).abs()
+            k = b * d * h * w
+            seen = [float((one / lim).max()) for lim in (R.bound_b("f16x3", k, ex), R.bound_c("f16x3", k, ex))]
+            with capsys.disabled():
+                print(f"\nfull size wgrad: one column counted twice would be (b) {seen[0]:.3g} (c) {seen[1]:.3g} times its bound")
+            assert seen[1] > 4.0, seen
+        else:
+            src, wk = (x, wt) if kind == "fwd" else (dy, wt.transpose(0, 1).flip(2, 3, 4))
+            pts = _sample_points(b, d, h, w, 4096, 7501)
+            ref = _sampled_reference(src, wk, pts)
+            sref = ref.pop("sref")
+            sel = got.permute(0, 2, 3, 4, 1)[pts[:, 0], pts[:, 1], pts[:, 2], pts[:, 3]]
+            r = R.check(sel, "f16x3", 27 * c, ref, sref, R.amax_of(src), R.amax_of(wt))
+        record("f16x3", kind, f"full size {kind} 32->32 {shape} f16x3 [{name}]", r, capsys)
+        assert max(r) <= 1.0, (kind, name, r)

@@ -50,8 +50,27 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("env,path,expr", CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in CASES])
-def test_route_behind_switch(env, path, expr):
+# The stride-1 sweep against fp64 (tests/test_gpu_conv3d_s1.py) behind every switch that changes one of its routes; each
+# selection also runs that file's route-coverage test under the switch.
+S1 = "tests/test_gpu_conv3d_s1.py"
+S1_WGRAD = "stride1_vs_fp64 and wgrad and not fp32 or presplit_operands or accumulate_only or every_route"
+S1_CASES = [
+    ({"AZ_WGRAD_R16_WGS": "3"}, S1, S1_WGRAD),                   # the column walk at every shape with more than 3 columns
+    ({"AZ_WGRAD_R16_WGS": "8"}, S1, S1_WGRAD),                   # wgs % 8 == 0: the XCD column map at small shapes
+    ({"AZ_WGRAD_R16_WGS": "64"}, S1, "stride1_vs_fp64 and wgrad and 1x24x5x352 or every_route"),  # the cap takes effect
+    ({"AZ_WGRAD_R16_XCD": "0"}, S1, S1_WGRAD + " or full_size"),
+    ({"AZ_WGRAD_R16_WIDE": "1"}, S1, S1_WGRAD + " or full_size"),
+    ({"AZ_WGRAD_R16": "0"}, S1, "stride1_vs_fp64 and wgrad and bf16x6 or every_route"),  # one-kd-per-wave bf16x6 kernels
+    ({"AZ_WGRAD_R16": "1"}, S1, "stride1_vs_fp64 and wgrad and bf16x6 or every_route"),
+    ({"AZ_WGRAD_R16": "0", "AZ_WGRAD_FW": "0"}, S1, "stride1_vs_fp64 and wgrad and bf16x6 or every_route"),
+    ({"AZ_CONV_ROLL": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and bf16x6 and not wgrad or every_route"),  # m128
+    ({"AZ_CONV_ROLL": "0", "AZ_CONV_M128": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and bf16x6 and not wgrad or every_route"),
+    ({"AZ_CONV_ROLL64": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and f16x3 and 64x64 and not wgrad or every_route"),
+    ({"AZ_ROLL_SEGLEN": "1"}, S1, "stride1_vs_fp64 and not wgrad and not fp32 or residual_handover or dgrad_presplit or full_size"),
+]
+
+
+def _child(env, path, expr):
     cmd = [sys.executable, "-m", "pytest", path, "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"]
     if expr:
         cmd += ["-k", expr]
@@ -59,6 +78,16 @@ def test_route_behind_switch(env, path, expr):
     tail = (r.stdout + r.stderr)[-1500:]
     assert r.returncode == 0, tail
     assert " passed" in r.stdout and "no tests ran" not in r.stdout, tail
+
+
+@pytest.mark.parametrize("env,path,expr", CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in CASES])
+def test_route_behind_switch(env, path, expr):
+    _child(env, path, expr)
+
+
+@pytest.mark.parametrize("env,path,expr", S1_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in S1_CASES])
+def test_stride1_sweep_behind_switch(env, path, expr):
+    _child(env, path, expr)
 
 
 def test_switches_are_read_once_into_the_options_struct():
