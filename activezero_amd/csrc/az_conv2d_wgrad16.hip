@@ -249,7 +249,7 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
 // once for all of the wave's taps -- 16 + 5 x 4 = 36 reads per 60 MFMAs (0.6 per MFMA against 1.48).  80 accumulator registers.
 // f16x3 only (the default arithmetic of the training step); everything else stays on the kernel above.
 // MEASURED (tools/wgrad2d_probe.py, B = 8, 136 x 240, alone, incl. the 5 us memset and the 5 us unpack): 103.2 us against 102.6 us
-// for the kernel above -- no gain, and the timing-only builds (X16_ABL) say why: without the atomic flush 67.5 us, without the
+// for the kernel above -- no gain, and the timing-only builds say why: without the atomic flush 67.5 us, without the
 // global loads 97.3, without both 54.0.  A 19 GFLOP launch split over 256 workgroups ends in 256 x 9 x 64 x 64 = 9.4 M float
 // atomics, which the memory side retires in ~35 us whatever produced them (the kernel above: 768 workgroups x 9 x 32 x 32 = 7.1 M):
 // BOTH kernels are flush-bound at this size, not LDS- or MFMA-bound.  In the step these launches sit on the side stream with
@@ -262,9 +262,6 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
 #define X16_LDS (2 * X16_CBUF + V16_RING * X16_FROW)  // 44 032 B
 #define X16_NQ ((2 * V16_POS + 2 * V16_FW) * 16)      // float4 pieces per step: 1 088
 #define X16_NLD 3                                      // per thread (512 threads)
-#ifndef X16_ABL
-#define X16_ABL 0  // timing-only builds: 1 no atomic flush, 2 no global loads, 4 one column per workgroup only (no second prologue)
-#endif
 
 __global__ void __launch_bounds__(512, 1)
 conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
@@ -337,7 +334,6 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
                     const int k = q >> 4, row = crow0 + (k >> 4), cw = cw0 + (k & 15);
                     if (with_coarse && row < h1 && cw < a.W)
                         off = (unsigned)(row * a.W + cw) * (unsigned)(a.cs_c * 4) + (unsigned)(q & 15) * 16u;
-                    if (X16_ABL & 2) off = V16_OOB;
                     pre[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_c, off, 0, 0);
                 } else {
                     const int f = q - 512;
@@ -345,7 +341,6 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
                     const int fr = frow0 + j, fw = cw0 - 1 + pp;
                     if (q < X16_NQ && (unsigned)fr < (unsigned)a.H && (unsigned)fw < (unsigned)a.W)
                         off = (unsigned)(fr * a.W + fw) * (unsigned)(a.cs_f * 4) + (unsigned)(q & 15) * 16u;
-                    if (X16_ABL & 2) off = V16_OOB;
                     pre[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_f, off, 0, 0);
                 }
             }
@@ -446,8 +441,7 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = 16 * mb + 4 * (lane >> 4) + r;
-                if (!(X16_ABL & 1) || acc[i][mb][r] == 123.456f)
-                    atomicAdd(&a.ws[((size_t)t * 64 + m) * 64 + 16 * nb + (lane & 15)], acc[i][mb][r] * o_scale);
+                atomicAdd(&a.ws[((size_t)t * 64 + m) * 64 + 16 * nb + (lane & 15)], acc[i][mb][r] * o_scale);
             }
     }
 }

@@ -163,19 +163,17 @@ conv3d_m128_kernel(const ConvArgs a) {
 #pragma unroll
         for (int p = 0; p < 3; ++p) aq[p] = *reinterpret_cast<const float4 *>(ap + 8 * p);
     };
-    // fp32 product on the bf16 pipe, one accumulator rounding per K16 block (az_common.h az_mfma6_step)
-    // (M1_PIPE 1 = two alternating temporaries, adds one block late: needs 32 more registers than the
-    //  2-waves/SIMD budget has left here; 0 = one temporary, added at once: the adds wait for the block's
-    //  last MFMA and the SIMD's other wave fills the gap)
-#ifndef M1_PIPE
-#define M1_PIPE 0
-#endif
+    // fp32 product on the bf16 pipe, one accumulator rounding per K16 block (az_common.h az_mfma6_now:
+    //  one temporary, added at once: the adds wait for the block's last MFMA and the SIMD's other wave
+    //  fills the gap.  az_mfma6_step's two alternating temporaries tn / tp, added one block late, need 32
+    //  more registers than the 2-waves/SIMD budget has left here.  The unused pair stays in step's
+    //  signature: without it hipcc schedules the kernel differently, and the recorded timings are of
+    //  this instruction order)
     f32x16 t0, t1;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { t0[e] = 0.f; t1[e] = 0.f; }
     auto step = [&](int cur, f32x16 &tn, const f32x16 &tp, const float4 (&aq)[3], const float4 (&bq)[3]) {
-        if (M1_PIPE) az_mfma6_step(tn, aq, bq, acc[(cur + 3) & 3], tp);
-        else az_mfma6_now(acc[cur], aq, bq);
+        az_mfma6_now(acc[cur], aq, bq);
     };
 
     // ---- software pipeline ------------------------------------------------------------------
@@ -228,7 +226,6 @@ conv3d_m128_kernel(const ConvArgs a) {
         bcur = bnext;
     }
 
-    if (M1_PIPE) acc[3] += t1;  // the last block's temporary
     // ---- epilogue -----------------------------------------------------------------------------
     // C/D map of the 32x32 MFMA: column (out channel) = lane & 31, row (voxel of the 4x8 tile) =
     // (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); M-tile m covers rows 4(m>>1).., cols 8(m&1)..

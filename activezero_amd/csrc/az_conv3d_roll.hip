@@ -41,9 +41,6 @@
 
 // Diagnostic build only (-DR16_STAMP): shader cycles per wave, summed into a buffer nothing else reads
 // (tools/roll_stamp_probe.py): [0] prologue, [1] stage bodies, [2] stage-end barriers, [3] tail, [8] kernel, [9] waves.
-#ifndef R16H_ABL
-#define R16H_ABL 0  // timing-only builds of the f16x3 stage: 1 no slab staging, 2 no weight refills, 4 no output stores, 8 no fragment refills
-#endif
 #ifdef R16_STAMP
 __device__ unsigned long long r16_stamp_sum[10];
 extern "C" int az_debug_roll_stamps(unsigned long long *out10, int reset) {
@@ -287,7 +284,7 @@ conv3d_roll_kernel(const ConvArgs a) {
         const unsigned tile_id = (unsigned)(((b * a.nseg + seg) * a.tiles_y + tiy4) * a.tiles_x + tix);
         const unsigned ch = co0 + wn * 16 + (lane & 15);
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(n * mean, fmaxf(m2, 0.f))), rs_part,
-                                              (tile_ok && lane < 16 && !R16_NOPART) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB, 0, 0);
+                                              (tile_ok && lane < 16) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB, 0, 0);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, n), rs_cnt,
                                               (tile_ok && lane == 0 && wn == 0 && co0 == 0) ? tile_id * 4u : R_OOB, 0, 0);
     };
@@ -413,7 +410,7 @@ conv3d_roll_kernel(const ConvArgs a) {
                 y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
             }
             if (EPI != 1) { y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_); }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, (R16H_ABL & 4) ? R_OOB : off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
             if (EPI == 1) {
                 h_n += vok ? 1 : 0;
                 const float v[4] = {y.x, y.y, y.z, y.w};
@@ -449,7 +446,7 @@ conv3d_roll_kernel(const ConvArgs a) {
             ntot = n;
             const unsigned ch = (unsigned)(cqh + r);
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(n * mean, fmaxf(m2, 0.f))), rs_part,
-                                                  (tile_ok && (lane & 15) == 0 && !R16_NOPART) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB, 0, 0);
+                                                  (tile_ok && (lane & 15) == 0) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB, 0, 0);
         }
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ntot), rs_cnt,
                                               (tile_ok && lane == 0 && wn == 0 && co0 == 0) ? tile_id * 4u : R_OOB, 0, 0);
@@ -504,21 +501,21 @@ conv3d_roll_kernel(const ConvArgs a) {
                         // the temporary carried in belongs to the chain before (a zero at the stage start)
                         f32x4 &prev = mm > 0 ? acc[kd][m - 1] : kd > 0 ? acc[kd - 1][m + 1] : pr > 0 ? acc[2][1] : acc[2][3];
                         r16_chain9(tq[q & 1], ah[mm], wh[kd], prev, tq[(q + 1) & 1]);
-                        if (kd == 2 && !(kh == 2 && pr == 1) && !(R16H_ABL & 8)) {  // this tile's fragments: the next pair's / next row's
+                        if (kd == 2 && !(kh == 2 && pr == 1)) {  // this tile's fragments: the next pair's / next row's
                             __builtin_amdgcn_sched_barrier(0);
                             load_ah(pr == 0 ? m + 2 : mm, pr == 0 ? kh : kh + 1);
                         }
-                        if (pr == 1 && mm == 1 && !(R16H_ABL & 2)) {  // last use of this row's (kd) weights: the next row's, or the next stage's first
+                        if (pr == 1 && mm == 1) {  // last use of this row's (kd) weights: the next row's, or the next stage's first
                             __builtin_amdgcn_sched_barrier(0);
                             load_bh(wh[kd], kh < 2 ? wcur + (kd * 9 + (kh + 1) * 3) * TAPF4 : wnxt + (kd * 9) * TAPF4);
                         }
                         // the next slab in two halves of three pieces (12 registers in flight instead of 24): requested at
                         // chains 1 / 16, split and written at chains 10, 12, 14 / 26, 28, 30
-                        if ((q == 1 || q == 16) && !(R16H_ABL & 1)) {
+                        if (q == 1 || q == 16) {
                             __builtin_amdgcn_sched_barrier(0);
                             issue(pn, CCN, q == 1 ? 0 : 3, q == 1 ? 3 : R_NLD);
                         }
-                        if (((q >= 10 && q <= 14 && !(q & 1)) || (q >= 26 && q <= 30 && !(q & 1))) && !(R16H_ABL & 1)) {
+                        if ((q >= 10 && q <= 14 && !(q & 1)) || (q >= 26 && q <= 30 && !(q & 1))) {
                             __builtin_amdgcn_sched_barrier(0);
                             commit_piece(q < 16 ? (q - 10) / 2 : 3 + (q - 26) / 2, sn);
                         }

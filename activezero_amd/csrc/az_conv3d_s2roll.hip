@@ -27,12 +27,12 @@
 // after the walk: one row per workgroup.
 // Measured (B = 4, V0 -> V1, alone): 0.34 ms forward with partials, 0.37 ms input gradient from a pre-split operand (gather
 // kernel: 0.59 / 0.55); counter passes 1.01 GB read + 0.20 GB written, clock 2.03 GHz, MFMA pipe 0.42.  Timing-only builds
-// (S2R_ABL, profiles/r05v_s2roll_ablations_corrected.txt): without the staging loads 0.226, without fragment reads 0.316,
+// (profiles/r05v_s2roll_ablations_corrected.txt): without the staging loads 0.226, without fragment reads 0.316,
 // without weight loads 0.320, all three off 0.222 -- against 0.122 ms of matrix time.  The plane loads are the exposed term:
 // a workgroup cannot request plane z + 1 while it multiplies plane z (vmcnt is one in-order counter: the weight fragments
 // requested behind the plane would wait for it; 72 prefetch registers do not exist beside 64 accumulators and two fragment
 // sets) and the second workgroup does not fill the gap: delayed starts of the workgroups in a CU's second slot, and three
-// workgroups per CU on 4 x 16 patches (-DS2R_TY=4: 168 registers, 43.5 KB), both leave the time where it is.
+// workgroups per CU on 4 x 16 patches (S2R_TY 4: 168 registers, 43.5 KB), both leave the time where it is.
 #include <type_traits>
 
 #include "az_conv3d_args.h"
@@ -41,12 +41,10 @@
 #include "az_launch_math.h"
 
 #define S2R_NT 256
-#ifndef S2R_TY
-#define S2R_TY 8                           // coarse rows of a patch: 8 (two workgroups per CU) or 4 (three; experiment)
-#endif
+#define S2R_TY 8                           // coarse rows of a patch
 #define S2R_NH (S2R_TY / 4)                // 4-row halves of the patch
 #define S2R_NTILE (4 * S2R_NH)             // 4x4 tiles of the patch = tiles per wave
-#define S2R_WGS (S2R_TY == 8 ? 2 : 3)      // workgroups per CU
+#define S2R_WGS 2                          // workgroups per CU
 #define S2R_FY (2 * S2R_TY + 1)            // fine rows / columns of a patch's plane (with the halo)
 #define S2R_FX 33                          // (561 voxels per staged plane at 8 patch rows)
 #define S2R_NLD (S2R_FY + 1)               // 16-byte pieces per thread and plane: one per fine row + the 33rd column
@@ -54,14 +52,6 @@
 #define S2R_SUB_BYTES ((S2R_TY + 1) * S2R_PITCH * 128)  // 19 584
 #define S2R_LDS (4 * S2R_SUB_BYTES)        // 78 336
 #define S2R_TAPB (4 * 2 * 64 * 16)         // bytes per tap of the packed image [tap][cout/16 (4)][part (2)][lane][16 B]
-#define S2R_SYNC() do { if (!(S2R_ABL & 32)) __syncthreads(); } while (0)
-#ifndef S2R_KIND_FIRST  // (experiments: 1 = the first / last plane of a segment multiply all eighteen taps, nine of them dropped)
-#define S2R_KIND_FIRST 2
-#define S2R_KIND_LAST 3
-#endif
-#ifndef S2R_ABL
-#define S2R_ABL 0  // timing-only ablations: 1 no output stores, 2 no weight loads after the first tap, 4 no slab staging, 8 no fragment reads, 16 no split / LDS writes, 32 no barriers
-#endif
 
 // Diagnostic build only (-DS2R_STAMP): per-phase cycle sums of every wave, added to a global array nothing else reads
 // (tools/s2roll_stamp_probe.py): 0 staging loads issued -> arrived, 1 split + LDS writes, 2 barrier behind the staging,
@@ -130,7 +120,7 @@ conv3d_s2roll_kernel(const ConvArgs a) {
     const unsigned dst_e = dst_col + oct_e, dst_o = dst_col + oct_o, dst_e_lo = dst_e ^ 64u, dst_o_lo = dst_o ^ 64u;
     auto stage = [&](int z) __attribute__((always_inline)) {
         u32x4 pre[S2R_NLD];
-        const bool zok = (unsigned)z < (unsigned)a.Di && !(S2R_ABL & 4);
+        const bool zok = (unsigned)z < (unsigned)a.Di;
         const int ih0 = 2 * ty0 - 1;
         const unsigned plane_off = (unsigned)(z * a.Hi) * (unsigned)a.Wi * 128u;
 #pragma unroll
@@ -158,20 +148,16 @@ conv3d_s2roll_kernel(const ConvArgs a) {
             const int base = (it & 1) * 2 * S2R_SUB_BYTES + r * S2R_PITCH * 128;
             uint2 hi, lo;
             az_stage_f16x4<PS>(pre[it], in_scale, hi, lo);
-            if (!(S2R_ABL & 16)) {
-                *reinterpret_cast<uint2 *>(slab + base + d_hi) = hi;
-                *reinterpret_cast<uint2 *>(slab + base + d_lo) = lo;
-            }
+            *reinterpret_cast<uint2 *>(slab + base + d_hi) = hi;
+            *reinterpret_cast<uint2 *>(slab + base + d_lo) = lo;
         }
         if (pc < S2R_FY) {
             const int r = pc >> 1;  // column 32 = c 16 of the even-column sub-slabs: part swap bit (16 >> 1) & 1 = 0
             unsigned char *dst = slab + (pc & 1) * 2 * S2R_SUB_BYTES + (r * S2R_PITCH + 16) * 128 + (pj & 1) * 8 + ((r & 1) ? oct_o : oct_e);  // (128-byte aligned base: + 64 below = ^ 64)
             uint2 hi, lo;
             az_stage_f16x4<PS>(pre[S2R_FY], in_scale, hi, lo);
-            if (!(S2R_ABL & 16)) {
-                *reinterpret_cast<uint2 *>(dst) = hi;
-                *reinterpret_cast<uint2 *>(dst + 64) = lo;
-            }
+            *reinterpret_cast<uint2 *>(dst) = hi;
+            *reinterpret_cast<uint2 *>(dst + 64) = lo;
         }
     };
 
@@ -220,11 +206,11 @@ conv3d_s2roll_kernel(const ConvArgs a) {
             float4 y = EPI == 1 ? make_float4(c[0] * osc, c[1] * osc, c[2] * osc, c[3] * osc)
                                 : make_float4(fmaf(c[0], sch.x, sfh.x), fmaf(c[1], sch.y, sfh.y), fmaf(c[2], sch.z, sfh.z), fmaf(c[3], sch.w, sfh.w));
             if (EPI == 0) {
-                const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, (S2R_ABL & 1) ? R_OOB : off, 0, 0));
+                const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0));
                 y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
                 y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_);
             }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, (S2R_ABL & 1) ? R_OOB : off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
             if (EPI == 1) {
                 h_n += vok ? 1 : 0;
                 const float d0 = vok ? y.x - hk[0] : 0.f, d1 = vok ? y.y - hk[1] : 0.f, d2 = vok ? y.z - hk[2] : 0.f, d3 = vok ? y.w - hk[3] : 0.f;
@@ -247,19 +233,14 @@ conv3d_s2roll_kernel(const ConvArgs a) {
     };
     // the voxel fragments of tap position i for the four tiles of patch half `half`: [tile][part]
     auto load_x = [&](float4 (&x)[4][2], int i, int half) __attribute__((always_inline)) {
+        (void)lane;  // (captured and unused: without it hipcc orders the kernel's instructions differently from the build the timings above are of)
         const int kh = i / 3, kw = i - 3 * kh;
         const int sub = (kh == 1 ? 2 : 0) + (kw == 1 ? 1 : 0);
         const int cst = sub * S2R_SUB_BYTES + 4 * half * S2R_PITCH * 128;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (S2R_ABL & 8) {
-                // (operands that differ per tile and lane: with one constant the accumulators of the tiles are provably equal
-                //  and the compiler keeps ONE chain of MFMAs -- the first ablation run, profiles/r05v_s2roll_ablations.txt)
-                x[q][0] = x[q][1] = __builtin_bit_cast(float4, u32x4{0x3c003c00u + (unsigned)(4 * half + q), 0x3c003c00u + (unsigned)lane, 0x3c003c00u, 0x3c003c00u});
-            } else {
-                x[q][0] = *reinterpret_cast<const float4 *>(slab + xb[kw == 1 ? 1 : 0][kh == 2][kw == 2] + cst + 4 * q * 128);
-                x[q][1] = *reinterpret_cast<const float4 *>(slab + xb[kw == 1 ? 0 : 1][kh == 2][kw == 2] + cst + 4 * q * 128);
-            }
+            x[q][0] = *reinterpret_cast<const float4 *>(slab + xb[kw == 1 ? 1 : 0][kh == 2][kw == 2] + cst + 4 * q * 128);
+            x[q][1] = *reinterpret_cast<const float4 *>(slab + xb[kw == 1 ? 0 : 1][kh == 2][kw == 2] + cst + 4 * q * 128);
         }
     };
     // twelve MFMAs: one weight fragment pair x four tiles (the three products of a tile are four MFMAs apart)
@@ -289,21 +270,20 @@ conv3d_s2roll_kernel(const ConvArgs a) {
             const int i = st / S2R_NH, g = st % S2R_NH;
             __builtin_amdgcn_sched_barrier(0);
             if (st + 1 < 9 * S2R_NH) load_x(xf[(st + 1) & 1], (st + 1) / S2R_NH, (st + 1) % S2R_NH);
-            if (g == 0 && i + 1 < 9 && !(S2R_ABL & 2)) {
+            if (g == 0 && i + 1 < 9) {
                 if (HAS_A) load_w(wa[(i + 1) & 1], KD_A, i + 1);
                 if (HAS_B) load_w(wb[(i + 1) & 1], 0, i + 1);
             }
             __builtin_amdgcn_sched_barrier(0);
-            const int wp = (S2R_ABL & 2) ? 0 : (i & 1);
-            if (HAS_A) mul4(acc[0], g, wa[wp], xf[st & 1]);
-            if (HAS_B) mul4(acc[1], g, wb[wp], xf[st & 1]);
+            if (HAS_A) mul4(acc[0], g, wa[i & 1], xf[st & 1]);
+            if (HAS_B) mul4(acc[1], g, wb[i & 1], xf[st & 1]);
         }
     };
 
     // ---- the walk: fine planes 2 c0 - 1 .. 2 c1 - 1 ------------------------------------------------------------------------
     stage(2 * c0 - 1);
     __syncthreads();
-    plane(std::integral_constant<int, S2R_KIND_FIRST>{});
+    plane(std::integral_constant<int, 2>{});
 #pragma unroll
     for (int m = 0; m < S2R_NTILE; ++m) {
         acc[0][m] = acc[1][m];
@@ -311,22 +291,22 @@ conv3d_s2roll_kernel(const ConvArgs a) {
     }
     for (int t = c0; t < c1; ++t) {
         S2R_T(3);
-        S2R_SYNC();
+        __syncthreads();
         S2R_T(4);
         stage(2 * t);
         S2R_T(1);
-        S2R_SYNC();
+        __syncthreads();
         S2R_T(2);
         plane(std::integral_constant<int, 0>{});
         S2R_T(3);
-        S2R_SYNC();
+        __syncthreads();
         S2R_T(4);
         stage(2 * t + 1);
         S2R_T(1);
-        S2R_SYNC();
+        __syncthreads();
         S2R_T(2);
         if (t + 1 < c1) plane(std::integral_constant<int, 1>{});
-        else plane(std::integral_constant<int, S2R_KIND_LAST>{});
+        else plane(std::integral_constant<int, 3>{});
         S2R_T(3);
         finish(t);
         S2R_T(5);

@@ -24,7 +24,7 @@
 //     second half; one barrier per stage.
 // Measured (B = 4, V1 -> V0, alone): 0.46 ms for either use (az_conv3d_t2.hip: 0.58 / 0.72; 0.49-0.51 before the closing stage
 // of a segment was cut down to its nine kd = 0 taps).  Counter pass (profiles/r04_pmc_*_b4.json): 0.27 GB read + 0.80 GB written
-// for 0.20 + 0.80 algorithmic, clock 2.19 GHz, MFMA pipe 0.29-0.30 busy.  Timing-only builds (T2R_ABL, 0.46 shipped on that box):
+// for 0.20 + 0.80 algorithmic, clock 2.19 GHz, MFMA pipe 0.29-0.30 busy.  Timing-only builds (0.46 shipped on that box):
 // without the output stores 0.36, with only the first two taps' weight loads per stage 0.31, without slab staging 0.41, without
 // fragment reads 0.46; stores + weights + staging all off: 0.163 ms -- the matrix work itself at 0.8 of the pipe.  So the four
 // costs ADD: matrix 0.16 + weight fragments 0.15 + output stores 0.10-0.13 + staging 0.05.  The weight term is L1 bandwidth:
@@ -47,9 +47,6 @@
 #define T2R_LDS (4 * R_SLAB_BYTES)       // [plane buffer][chunk]
 #define T2R_TAPF4 (2 * 2 * 2 * 64)       // float4 per tap of the packed image [tap][cc(2)][n16(2)][part(2)][lane]
 #define T2R_CCF4 (2 * 2 * 64)
-#ifndef T2R_ABL
-#define T2R_ABL 0  // timing-only ablations: 1 no output stores / residual loads, 2 the weights of a stage's first two taps only, 4 no slab staging, 8 no fragment reads
-#endif
 
 __host__ __device__ constexpr int t2r_k(int p, int o) { return p == 0 ? 1 : (o == 0 ? 2 : 0); }
 // the 27 taps of a stage in chain order: row offset oh, kd group g (0: kd = 0 into the carried set, 1: kd = 1, 2: kd = 2
@@ -193,11 +190,11 @@ conv3d_t2roll_kernel(const ConvArgs a) {
                 float4 y = EPI == 1 ? make_float4(c[0] * osc, c[1] * osc, c[2] * osc, c[3] * osc)
                                     : make_float4(fmaf(c[0], sch.x, sfh.x), fmaf(c[1], sch.y, sfh.y), fmaf(c[2], sch.z, sfh.z), fmaf(c[3], sch.w, sfh.w));
                 if (EPI == 0) {
-                    const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, (T2R_ABL & 1) ? R_OOB : off, 0, 0));
+                    const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0));
                     y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
                     y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_);
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, (T2R_ABL & 1) ? R_OOB : off, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
                 if (EPI == 1) {
                     h_n += vok ? 1 : 0;
                     const float d0 = vok ? y.x - hk[0] : 0.f, d1 = vok ? y.y - hk[1] : 0.f, d2 = vok ? y.z - hk[2] : 0.f, d3 = vok ? y.w - hk[3] : 0.f;
@@ -237,7 +234,7 @@ conv3d_t2roll_kernel(const ConvArgs a) {
         finish(1, 2 * z - 2, z - 1 >= c0);
         rotate();
         __builtin_amdgcn_sched_barrier(0);
-        if (!(T2R_ABL & 4) && !CLOSE) issue(z + 1);
+        if (!CLOSE) issue(z + 1);
         float4 xf[2][2][2];  // [tile][ow][part] of the current (chunk, oh)
         int chain = 0;       // (static after unrolling)
         int k = 0;           // taps multiplied so far: the parity of the weight buffers
@@ -266,7 +263,7 @@ conv3d_t2roll_kernel(const ConvArgs a) {
                 {
                     const int nx = CLOSE ? e.nxc : i + 1;                      // next tap of this chunk (27: the chunk is done)
                     const int ni = nx < 27 ? nx : 0, ncc = nx < 27 ? cc : cc + 1;  // (entry 0 has g = 0: first in both forms)
-                    if (!(CLOSE && ncc == 2) && !((T2R_ABL & 2) && k > 1)) load_w(wk[(k + 1) & 1], T.e[ni].tap * T2R_TAPF4 + (ncc & 1) * T2R_CCF4);
+                    if (!(CLOSE && ncc == 2)) load_w(wk[(k + 1) & 1], T.e[ni].tap * T2R_TAPF4 + (ncc & 1) * T2R_CCF4);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 f32x4 &t0 = tq[chain & 1][0], &t1 = tq[chain & 1][1];
@@ -287,7 +284,7 @@ conv3d_t2roll_kernel(const ConvArgs a) {
                 // the next plane: one piece behind every fourth tap of the second chunk
                 if (!CLOSE && cc == 1 && i >= 3 && i < 27 && (i - 3) % 4 == 0 && (i - 3) / 4 < T2R_NLD) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if (!(T2R_ABL & 4)) commit_piece((i - 3) / 4, pn);
+                    commit_piece((i - 3) / 4, pn);
                 }
             }
         }

@@ -48,9 +48,6 @@ typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 #define W16_NQ (W16_NPOS * 8)                              // float4 pieces: 1 120
 #define W16_NLD ((W16_NQ + 255) / 256)                     // 5 per thread
 #define W16_OOB 0xffffff00u
-#ifndef W16_TWO_CHAINS
-#define W16_TWO_CHAINS 0  // experiment: two independent MFMA chains per tap
-#endif
 
 struct Wg16Args {
     const float *coarse, *fine;
@@ -240,23 +237,12 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
                     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bq[1]), c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bq[0]), c, 0, 0, 0);
                 } else {
-#if W16_TWO_CHAINS
-                f32x4 u = {0.f, 0.f, 0.f, 0.f};
-                u = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bq[0], u, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[2], c, 0, 0, 0);
-                u = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[1], u, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[0], c, 0, 0, 0);
-                u = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[1], u, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[0], c, 0, 0, 0);
-                c += u;
-#else
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bq[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[0], c, 0, 0, 0);
-#endif
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bq[0], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[2], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[1], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[0], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[1], c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[0], c, 0, 0, 0);
                 }
                 acc[t] = c;
                 // the set of step s+1 (requested a step ago): one piece after each of the taps 1, 3, 5, 7, 9; then the
@@ -512,10 +498,6 @@ int az_conv3d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine
     a.wgs = best;
     a.xcd = az_options().wgrad_r16_xcd;
     const dim3 grid((unsigned)(a.wgs * ntiles));
-#ifdef WG16_SKIP  // timing-only build: the launch is left out (the workspace stays zero: those weights do not move) -- what the step
-                  // would gain if these weight gradients were free (tools/abl_step_sensitivity.sh); -DWG16_SKIP=1: the V0 shapes only
-    if (WG16_SKIP == 2 || (long long)D * H * W >= 1000000) return AZ_OK;
-#endif
     if (!(coarse_amax && fine_amax)) {
         if (split_mask) return AZ_EINVAL;
         hipLaunchKernelGGL(conv3d_wgrad_r16_kernel<0>, grid, dim3(256), 0, s, a);

@@ -26,7 +26,7 @@
 //     barrier per step; loads, zero padding and therefore vmcnt bookkeeping go through buffer instructions with
 //     out-of-range offsets (a step is one basic block); the set of step s+2 is requested in two halves while step s is
 //     multiplied, the set of step s+1 is split and written two pieces per tap;
-//   * timing-only ablations (S2_ABL, tools/abl_wgrad_s2.sh; conv1's weight gradient, 0.37 ms on that box): no split / LDS
+//   * timing-only ablations (conv1's weight gradient, 0.37 ms on that box): no split / LDS
 //     writes 0.21, no MFMAs 0.24, no fine-fragment reads 0.38, every column on the same addresses (L2 hits) 0.34, no
 //     flush 0.35 -- the matrix work and the staging VALU work of a step add up instead of overlapping (HBM: 1.0-1.1 GB read for
 //     1.0 GB of operands).  Tried without effect: the request for step s+2 right behind each split pair instead of in two
@@ -59,9 +59,6 @@ typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 #define S2_NFQ (3 * 8 * S2_FROWQ)                   // fine pieces per step: 3 264
 #define S2_NLD 8                                    // pieces per thread and step: 1 coarse + 7 fine (the last one partial)
 #define S2_OOB 0xffffff00u
-#ifndef S2_ABL
-#define S2_ABL 0  // timing-only ablations (tools/abl_wgrad_s2.sh): 1 no global loads, 2 no split / LDS writes, 4 no fine-fragment reads, 8 no MFMAs, 16 no flush, 32 every column loads the same addresses (L2 hits)
-#endif
 
 struct Wg16s2Args {
     const float *coarse, *fine;
@@ -162,16 +159,14 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
             colok |= (ok ? 1u : 0u) << (i + 1);
         }
         // (unsigned arithmetic: the base may lie "before" the tensor, base + rel of a valid piece never does)
-        const unsigned gbase_f = (S2_ABL & 32) ? plane_f + 15u * vb_f : (unsigned)(2 * cd - 1) * plane_f + (unsigned)(2 * cw0 - 1) * vb_f;
-        const unsigned gbase_c = (S2_ABL & 32) ? plane_c + 8u * vb_c : (unsigned)cd * plane_c + (unsigned)cw0 * vb_c;
+        const unsigned gbase_f = (unsigned)(2 * cd - 1) * plane_f + (unsigned)(2 * cw0 - 1) * vb_f;
+        const unsigned gbase_c = (unsigned)cd * plane_c + (unsigned)cw0 * vb_c;
 
         u32x4 pre[S2_NLD];
-        const bool s_abl_first = col == wg0;
         auto issue = [&](int crow0, int frow0, int it0, int it1) {  // coarse rows crow0..+3, fine rows frow0..+7 (frow0 >= 0)
 #pragma unroll
             for (int it = it0; it < it1; ++it) {
                 unsigned off = S2_OOB;
-                if (S2_ABL & 1) { if (s_abl_first) pre[it] = u32x4{1u, 2u, 3u, 4u}; continue; }
                 if (it == 0) {
                     if ((colok & 1u) && crow0 + (int)((tid >> 4) >> 3) < a.Hc)
                         off = gbase_c + (unsigned)crow0 * (unsigned)a.Wc * vb_c + relc_g;
@@ -185,7 +180,6 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
             }
         };
         auto commit_piece = [&](int it, int cbuf_idx, int frow0) {
-            if (S2_ABL & 2) return;
             uint2 hi, lo;
             if (it == 0) az_stage_f16x4<(PSM & 1) != 0>(pre[it], c_scale, hi, lo);
             else az_stage_f16x4<(PSM & 2) != 0>(pre[it], f_scale, hi, lo);
@@ -243,21 +237,16 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
 #pragma unroll
             for (int t = 0; t < 7; ++t) {
                 __builtin_amdgcn_sched_barrier(0);
-                if (t + 1 < 7 && !((S2_ABL & 4) && s > 0)) load_b(bf[(t + 1) & 1], t + 1);
+                if (t + 1 < 7) load_b(bf[(t + 1) & 1], t + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 const az_f16x8(&bq)[2] = bf[t & 1];
                 // four independent chains, each lo*hi, hi*lo, hi*hi into the running accumulator (smallest first)
-                if (!(S2_ABL & 8)) {
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) acc[t][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][1], bq[0], acc[t][mb], 0, 0, 0);
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) acc[t][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][0], bq[1], acc[t][mb], 0, 0, 0);
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) acc[t][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][0], bq[0], acc[t][mb], 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int mb = 0; mb < 4; ++mb) acc[t][mb][0] += __builtin_bit_cast(float, (int)af[mb][0][0] ^ (int)bq[0][1]);  // keep the operands live
-                }
                 // the set of step s+1 (requested a step ago): two pieces behind each of four taps, and the request for the same
                 // two pieces of step s+2 as soon as their registers are free
                 if (t < 4) {
@@ -277,7 +266,6 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
     for (int t = 0; t < 7; ++t) {
         const int tap = tap0 + t;
         if (tap > 26) break;  // (wave-uniform)
-        if ((S2_ABL & 16) && a.B > 0) break;
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb)
 #pragma unroll

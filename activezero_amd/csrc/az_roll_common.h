@@ -15,9 +15,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #define R_SLAB_BYTES (R_SY * R_SX * R_VB)  // 34 560
 #define R_NQ (R_SY * R_SX * 8)             // 16-byte fp32 pieces of one plane chunk (8 per voxel)
 #define R_NLD ((R_NQ + 255) / 256)         // 6 per thread
-#ifndef R16_NOPART
-#define R16_NOPART 0  // timing-only build: BatchNorm partials not written
-#endif
 #define R_OOB 0xffffff00u                  // a buffer offset beyond every tensor: loads return 0, stores are dropped
 
 #define R_MF(ACC, A, B) __builtin_amdgcn_mfma_f32_16x16x32_bf16( \

@@ -294,11 +294,7 @@ softargmin_bwd_kernel(float *__restrict__ glogits, const float *__restrict__ gou
         if (v == 0.f) continue;
         const int gy = min(max(ybase + ly, 0), h - 1);
         const int gx = min(max(xbase + lx, 0), w - 1);
-#if defined(SA_DIAG) && (SA_DIAG & 2)
-        glogits[(((size_t)b * d + k) * h + gy) * w + gx] = v;
-#else
         atomicAdd(&glogits[(((size_t)b * d + k) * h + gy) * w + gx], v);
-#endif
     }
 }
 
