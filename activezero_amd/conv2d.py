@@ -21,8 +21,8 @@ import os
 
 import torch
 
-from . import _lib, conv3d, overlap, profiler
-from .conv3d import _cache_get, _cache_key, _cache_put
+from . import _lib, conv3d, overlap, packing, profiler
+from .amax import absmax, _get_amax, weight_amax
 from .ops import _call, _chk, _p, _stream
 
 _SAME = {(3, 3, 1), (3, 3, 2), (1, 1, 1), (3, 5, 1)}
@@ -42,21 +42,18 @@ def image(r):
 
 def _pack(weight, cin, cout, ci_real, co_real, s_out, s_in, kh, kw, flip, cache=False):
     w = _chk(weight.detach().contiguous(), "weight")
-    key = None
-    if cache:
-        key = (_cache_key(weight), cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip))
-        hit = _cache_get(_PACK2D_CACHE, key)
-        if hit is not None:
-            return hit[0]
-    n = _lib.lib().az_conv2d_packed_floats(cin, cout, kh, kw)
-    if n < 0:
-        raise RuntimeError(f"conv2d: unsupported channel counts cin={cin} cout={cout}")
-    packed = torch.empty(n, dtype=torch.float32, device=w.device)
-    _call("az_conv2d_pack_weights", _p(packed), _p(w), cin, cout, ci_real, co_real, s_out, s_in, kh, kw,
-          int(flip), _stream())
-    if key is not None:
-        _cache_put(_PACK2D_CACHE, key, (packed, weight), 256)
-    return packed
+
+    def make():
+        n = _lib.lib().az_conv2d_packed_floats(cin, cout, kh, kw)
+        if n < 0:
+            raise RuntimeError(f"conv2d: unsupported channel counts cin={cin} cout={cout}")
+        packed = torch.empty(n, dtype=torch.float32, device=w.device)
+        _call("az_conv2d_pack_weights", _p(packed), _p(w), cin, cout, ci_real, co_real, s_out, s_in, kh, kw,
+              int(flip), _stream())
+        return packed
+
+    key = (packing.cache_key(weight), cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip)) if cache else None
+    return packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
 
 
 PEAK_F16 = conv3d._PEAK_F16
@@ -65,37 +62,34 @@ PEAK_F16 = conv3d._PEAK_F16
 def _amax_of(t, r):
     """device scalar max |t| for the f16x3 kernels: what t's producer attached (BatchNorm apply / backward), else a pass
     over its rows r"""
-    am = conv3d._get_amax(t)
-    return am if am is not None else conv3d.absmax(r)
+    am = _get_amax(t)
+    return am if am is not None else absmax(r)
 
 
 def _pack_f16(weight, cin, cout, ci_real, co_real, s_out, s_in, kh, kw, flip, cache=False):
     """(packed f16x3 image, device scalar max |w|) -- az_conv2d_pack_weights_f16"""
     w = _chk(weight.detach().contiguous(), "weight")
-    key = None
+
+    def pack_now(packed, w_amax):
+        _call("az_conv2d_pack_weights_f16", _p(packed), _p(w), _p(w_amax), cin, cout, ci_real, co_real, s_out, s_in, kh, kw,
+              int(flip), _stream())
+
+    def make():
+        w_amax = weight_amax(weight, w)
+        packed = torch.empty(kh * kw * cin * cout, dtype=torch.float32, device=w.device)
+        pack_now(packed, w_amax)
+        return packed, w_amax
+
     if cache:
-        key = (_cache_key(weight), "f16", cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip))
-        hit = _cache_get(_PACK2D_CACHE, key)
-        if hit is not None:
-            return hit[0]
-    if not cache:
-        hit = conv3d._planned_pack(weight, w, conv3d.PACK_2D_SAME, cin, cout, ci_real, co_real, s_out, s_in, kh * kw, flip,
-                                   lambda packed, w_amax: _call("az_conv2d_pack_weights_f16", _p(packed), _p(w), _p(w_amax), cin,
-                                                                cout, ci_real, co_real, s_out, s_in, kh, kw, int(flip), _stream()))
-        if hit is not None:
-            return hit
-    w_amax = _w_amax(weight, w)
-    packed = torch.empty(kh * kw * cin * cout, dtype=torch.float32, device=w.device)
-    _call("az_conv2d_pack_weights_f16", _p(packed), _p(w), _p(w_amax), cin, cout, ci_real, co_real, s_out, s_in, kh, kw,
-          int(flip), _stream())
-    if key is not None:
-        _cache_put(_PACK2D_CACHE, key, ((packed, w_amax), weight), 256)
-    return packed, w_amax
+        key = (packing.cache_key(weight), "f16", cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip))
+        return packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
+    hit = packing.planned_pack(weight, w, packing.PACK_2D_SAME, cin, cout, ci_real, co_real, s_out, s_in, kh * kw, flip, pack_now)
+    return hit if hit is not None else make()
 
 
 def _run_f16(xr, x_amax, packed, w_amax, cin, cout, kh, kw, dil, scale=None, shift=None, res=None, relu=False,
              tag="conv2d", stats=None):
-    """_run / _run_stats on the f16x3 kernels"""
+    """_run on the f16x3 kernels"""
     b, h, w, cx = xr.shape
     out = xr.new_empty(b, h, w, cout)
     with profiler.scope(f"{tag}_{kh}x{kw}d{dil}_{cin}_{cout}", flops=2.0 * kh * kw * cin * cout * b * h * w,
@@ -129,40 +123,28 @@ def _roll_ok(xr, cin, cout, kh, kw, dil, res=None):
 
 def _pack_roll(weight, cin, cout, s_out, s_in, flip, cache=False):
     w = _chk(weight.detach().contiguous(), "weight")
-    key = None
-    if cache:
-        key = (_cache_key(weight), "roll", cin, cout, s_out, s_in, bool(flip))
-        hit = _cache_get(_PACK2D_CACHE, key)
-        if hit is not None:
-            return hit[0]
-    packed = torch.empty(int(_lib.lib().az_conv2d_roll_packed_floats(cin, cout)), dtype=torch.float32, device=w.device)
-    _call("az_conv2d_roll_pack", _p(packed), _p(w), cin, cout, s_out, s_in, int(flip), _stream())
-    if key is not None:
-        _cache_put(_PACK2D_CACHE, key, (packed, weight), 256)
-    return packed
 
+    def make():
+        packed = torch.empty(int(_lib.lib().az_conv2d_roll_packed_floats(cin, cout)), dtype=torch.float32, device=w.device)
+        _call("az_conv2d_roll_pack", _p(packed), _p(w), cin, cout, s_out, s_in, int(flip), _stream())
+        return packed
 
-def _w_amax(weight, w):
-    """amax array of a weight tensor, once per optimizer step (conv3d._W_AMAX)"""
-    wkey = (weight.data_ptr(), weight._version, weight.device.index, weight.numel())
-    hit = _cache_get(conv3d._W_AMAX, wkey)
-    if hit is not None:
-        return hit[0]
-    w_amax = conv3d.absmax(w)
-    _cache_put(conv3d._W_AMAX, wkey, (w_amax, weight), 512)
-    return w_amax
+    key = (packing.cache_key(weight), "roll", cin, cout, s_out, s_in, bool(flip)) if cache else None
+    return packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
 
 
 def _pack_roll_f16(weight, cin, cout, s_out, s_in, flip):
     w = _chk(weight.detach().contiguous(), "weight")
-    hit = conv3d._planned_pack(weight, w, conv3d.PACK_2D_ROLL, cin, cout, cin, cout, s_out, s_in, 9, flip,
-                               lambda packed, w_amax: _call("az_conv2d_roll_pack_f16", _p(packed), _p(w), _p(w_amax), cin, cout,
-                                                            s_out, s_in, int(flip), _stream()))
+
+    def pack_now(packed, w_amax):
+        _call("az_conv2d_roll_pack_f16", _p(packed), _p(w), _p(w_amax), cin, cout, s_out, s_in, int(flip), _stream())
+
+    hit = packing.planned_pack(weight, w, packing.PACK_2D_ROLL, cin, cout, cin, cout, s_out, s_in, 9, flip, pack_now)
     if hit is not None:
         return hit
-    w_amax = _w_amax(weight, w)
+    w_amax = weight_amax(weight, w)
     packed = torch.empty(9 * cin * cout, dtype=torch.float32, device=w.device)
-    _call("az_conv2d_roll_pack_f16", _p(packed), _p(w), _p(w_amax), cin, cout, s_out, s_in, int(flip), _stream())
+    pack_now(packed, w_amax)
     return packed, w_amax
 
 
@@ -184,52 +166,63 @@ def _run_roll_f16(xr, x_amax, packed, w_amax, cin, cout, res=None, tag="conv2d",
     return out
 
 
-def _run_roll(xr, packed, cin, cout, scale=None, shift=None, res=None, relu=False, tag="conv2d"):
+def _run_roll(xr, packed, cin, cout, scale=None, shift=None, res=None, relu=False, tag="conv2d", stats=None):
+    """the batch-walking 3x3 kernel (az_conv2d_roll.hip); `stats`: as _run"""
     b, h, w, _ = xr.shape
     out = xr.new_empty(b, h, w, cout)
+    if stats is not None:
+        nrows = int(_lib.lib().az_conv2d_roll_stats_rows(stats.groups, b, h, w, cin, cout))
+        if nrows <= 0:
+            raise RuntimeError(f"az_conv2d_roll_stats_rows: {nrows}")
+        part, cnt = xr.new_empty(stats.groups, cout, nrows, 2), xr.new_empty(stats.groups, nrows)
+        stats.part, stats.cnt, stats.tiles = part, cnt, nrows
     with profiler.scope(f"{tag}_3x3d1_{cin}_{cout}", flops=2.0 * 9 * cin * cout * b * h * w, peak=PEAK_X6):
-        _call("az_conv2d_roll_fwd", _p(out), _p(xr), _p(packed), _p(scale), _p(shift), _p(res), int(relu), b, h, w,
-              cin, cout, _stream())
+        if stats is not None:
+            _call("az_conv2d_roll_fwd_stats", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), stats.groups, b, h, w,
+                  cin, cout, _stream())
+        else:
+            _call("az_conv2d_roll_fwd", _p(out), _p(xr), _p(packed), _p(scale), _p(shift), _p(res), int(relu), b, h, w,
+                  cin, cout, _stream())
     return out
 
 
-def _run_roll_stats(xr, packed, cin, cout, stats):
-    b, h, w, _ = xr.shape
-    out = xr.new_empty(b, h, w, cout)
-    nrows = int(_lib.lib().az_conv2d_roll_stats_rows(stats.groups, b, h, w, cin, cout))
-    if nrows <= 0:
-        raise RuntimeError(f"az_conv2d_roll_stats_rows: {nrows}")
-    part, cnt = xr.new_empty(stats.groups, cout, nrows, 2), xr.new_empty(stats.groups, nrows)
-    with profiler.scope(f"conv2d_3x3d1_{cin}_{cout}", flops=2.0 * 9 * cin * cout * b * h * w, peak=PEAK_X6):
-        _call("az_conv2d_roll_fwd_stats", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), stats.groups, b, h, w,
-              cin, cout, _stream())
-    stats.part, stats.cnt, stats.tiles = part, cnt, nrows
-    return out
-
-
-def _run(xr, packed, cin, cout, kh, kw, dil, scale=None, shift=None, res=None, relu=False, tag="conv2d"):
-    """xr: [B,H,W,Cx] rows with Cx >= cin; returns [B,H,W,cout] rows."""
+def _run(xr, packed, cin, cout, kh, kw, dil, scale=None, shift=None, res=None, relu=False, tag="conv2d", stats=None):
+    """xr: [B,H,W,Cx] rows with Cx >= cin; returns [B,H,W,cout] rows.  `stats` (a bn2d.Partials): the launch without
+    epilogue operands that also fills it with the output's BatchNorm partials."""
     b, h, w, cx = xr.shape
     out = xr.new_empty(b, h, w, cout)
+    if stats is not None:
+        tiles = int(_lib.lib().az_conv2d_stats_tiles(b, h, w, stats.groups))
+        part, cnt = xr.new_empty(stats.groups, cout, tiles, 2), xr.new_empty(stats.groups, tiles)
+        stats.part, stats.cnt, stats.tiles = part, cnt, tiles
     with profiler.scope(f"{tag}_{kh}x{kw}d{dil}_{cin}_{cout}", flops=2.0 * kh * kw * cin * cout * b * h * w,
                         peak=PEAK_X6):
-        _call("az_conv2d_fwd", _p(out), _p(xr), _p(packed), _p(scale), _p(shift), _p(res), int(relu), b, h, w,
-              cin, cout, cx, cout, res.shape[-1] if res is not None else 0, kh, kw, dil, _stream())
+        if stats is not None:
+            _call("az_conv2d_fwd_stats", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), stats.groups, b, h, w, cin, cout,
+                  cx, cout, kh, kw, dil, _stream())
+        else:
+            _call("az_conv2d_fwd", _p(out), _p(xr), _p(packed), _p(scale), _p(shift), _p(res), int(relu), b, h, w,
+                  cin, cout, cx, cout, res.shape[-1] if res is not None else 0, kh, kw, dil, _stream())
     return out
 
 
-def _run_stats(xr, packed, cin, cout, kh, kw, dil, stats):
-    """_run without epilogue operands; also fills `stats` (bn2d.Partials) with the output's BatchNorm partials."""
-    b, h, w, cx = xr.shape
-    out = xr.new_empty(b, h, w, cout)
-    tiles = int(_lib.lib().az_conv2d_stats_tiles(b, h, w, stats.groups))
-    part, cnt = xr.new_empty(stats.groups, cout, tiles, 2), xr.new_empty(stats.groups, tiles)
-    with profiler.scope(f"conv2d_{kh}x{kw}d{dil}_{cin}_{cout}", flops=2.0 * kh * kw * cin * cout * b * h * w,
-                        peak=PEAK_X6):
-        _call("az_conv2d_fwd_stats", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), stats.groups, b, h, w, cin, cout,
-              cx, cout, kh, kw, dil, _stream())
-    stats.part, stats.cnt, stats.tiles = part, cnt, tiles
-    return out
+def _run_same(t, tr, weight, ci, co, kh, kw, dil, flip, f16, res=None, tag="conv2d", stats=None):
+    """One stride-1 "same" launch ci -> co on the rows tr of the tensor t: picks the kernel (_roll_ok) and the arithmetic
+    (f16), packs `weight` ([Cout,Cin,kh,kw]) for it and runs it.  flip = False: the layer's forward (ci, co = Cin, Cout);
+    flip = True: its input gradient, the same convolution with the taps flipped and the channel roles swapped
+    (ci, co = Cout, Cin)."""
+    taps = kh * kw
+    s_out, s_in = (taps, co * taps) if flip else (ci * taps, taps)  # strides of the co / ci index in the stored weight
+    roll = _roll_ok(tr, ci, co, kh, kw, dil, res)
+    if f16 and roll:
+        pk, w_amax = _pack_roll_f16(weight, ci, co, s_out, s_in, flip)
+        return _run_roll_f16(tr, _amax_of(t, tr), pk, w_amax, ci, co, res=res, tag=tag, stats=stats)
+    if f16:
+        pk, w_amax = _pack_f16(weight, ci, co, ci, co, s_out, s_in, kh, kw, flip)
+        return _run_f16(tr, _amax_of(t, tr), pk, w_amax, ci, co, kh, kw, dil, res=res, tag=tag, stats=stats)
+    if roll:
+        return _run_roll(tr, _pack_roll(weight, ci, co, s_out, s_in, flip), ci, co, res=res, tag=tag, stats=stats)
+    return _run(tr, _pack(weight, ci, co, ci, co, s_out, s_in, kh, kw, flip), ci, co, kh, kw, dil, res=res, tag=tag, stats=stats)
 
 
 def _wgrad(gr, xr, cm, cn, cm_real, cn_real, kh, kw, dil, tag="conv2d", sink=None, amax=None, late_ok=True):
@@ -254,8 +247,8 @@ def _wgrad(gr, xr, cm, cn, cm_real, cn_real, kh, kw, dil, tag="conv2d", sink=Non
                 _call("az_conv2d_wgrad", out, _p(ws), ws_bytes, _p(gr), _p(xr), b, h, w, cm, cn, cm_real, cn_real,
                       gr.shape[-1], xr.shape[-1], kh, kw, dil, _stream())
         else:
-            am_g = amax[0] if amax[0] is not None else conv3d.absmax(gr)
-            am_x = amax[1] if amax[1] is not None else conv3d.absmax(xr)
+            am_g = amax[0] if amax[0] is not None else absmax(gr)
+            am_x = amax[1] if amax[1] is not None else absmax(xr)
             with profiler.scope(f"{tag}_wgrad_{kh}x{kw}d{dil}_{cm}_{cn}", flops=2.0 * kh * kw * cm * cn * b * h * w,
                                 peak=PEAK_F16):
                 _call("az_conv2d_wgrad_f16", out, _p(ws), ws_bytes, _p(gr), _p(xr), _p(am_g), _p(am_x), b, h, w, cm, cn,
@@ -300,24 +293,11 @@ class _ConvSame(torch.autograd.Function):
         xr = _chk(rows(x), "x")
         with torch.cuda.device(x.device):
             want_stats = stats is not None and (kh, kw) in ((3, 3), (1, 1)) and xr.shape[0] % stats.groups == 0
-            if f16 and _roll_ok(xr, cin, cout, kh, kw, dil):
-                pk, w_amax = _pack_roll_f16(weight, cin, cout, cin * 9, 9, False)
-                y = _run_roll_f16(xr, _amax_of(x, xr), pk, w_amax, cin, cout, stats=stats if want_stats else None)
-            elif f16:
-                pk, w_amax = _pack_f16(weight, cin, cout, cin, cout, cin * kh * kw, kh * kw, kh, kw, False)
-                y = _run_f16(xr, _amax_of(x, xr), pk, w_amax, cin, cout, kh, kw, dil, stats=stats if want_stats else None)
-            elif _roll_ok(xr, cin, cout, kh, kw, dil):
-                pk = _pack_roll(weight, cin, cout, cin * 9, 9, False)
-                y = _run_roll_stats(xr, pk, cin, cout, stats) if want_stats else _run_roll(xr, pk, cin, cout)
-            else:
-                pk = _pack(weight, cin, cout, cin, cout, cin * kh * kw, kh * kw, kh, kw, False)
-                if want_stats:
-                    y = _run_stats(xr, pk, cin, cout, kh, kw, dil, stats)  # + the BatchNorm partials of y (bn2d.Partials)
-                else:
-                    y = _run(xr, pk, cin, cout, kh, kw, dil)
+            # (+ the BatchNorm partials of y, bn2d.Partials)
+            y = _run_same(x, xr, weight, cin, cout, kh, kw, dil, False, f16, stats=stats if want_stats else None)
         ctx.save_for_backward(xr, weight)
         ctx.dil = dil
-        ctx.x_amax = (conv3d._get_amax(x) if conv3d._get_amax(x) is not None else conv3d._get_amax(xr)) if f16 else None
+        ctx.x_amax = (_get_amax(x) if _get_amax(x) is not None else _get_amax(xr)) if f16 else None
         ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as a zero tensor
         if with_skip:
             return image(y), x.view_as(x)
@@ -335,23 +315,12 @@ class _ConvSame(torch.autograd.Function):
         with torch.cuda.device(gy.device):
             if ctx.needs_input_grad[0]:  # the same convolution, taps flipped, channel roles swapped
                 sk = _chk(rows(gskip), "grad_skip") if gskip is not None else None
-                if ctx.f16 and _roll_ok(gr, cout, cin, kh, kw, dil, sk):
-                    pk, w_amax = _pack_roll_f16(weight, cout, cin, 9, cin * 9, True)
-                    gx = image(_run_roll_f16(gr, _amax_of(gy, gr), pk, w_amax, cout, cin, res=sk, tag="dgrad2d"))
-                elif ctx.f16:
-                    pk, w_amax = _pack_f16(weight, cout, cin, cout, cin, kh * kw, cin * kh * kw, kh, kw, True)
-                    gx = image(_run_f16(gr, _amax_of(gy, gr), pk, w_amax, cout, cin, kh, kw, dil, res=sk, tag="dgrad2d"))
-                elif _roll_ok(gr, cout, cin, kh, kw, dil, sk):
-                    pk = _pack_roll(weight, cout, cin, 9, cin * 9, True)
-                    gx = image(_run_roll(gr, pk, cout, cin, res=sk, tag="dgrad2d"))
-                else:
-                    pk = _pack(weight, cout, cin, cout, cin, kh * kw, cin * kh * kw, kh, kw, True)
-                    gx = image(_run(gr, pk, cout, cin, kh, kw, dil, res=sk, tag="dgrad2d"))
+                gx = image(_run_same(gy, gr, weight, cout, cin, kh, kw, dil, True, ctx.f16, res=sk, tag="dgrad2d"))
             if ctx.needs_input_grad[1]:
                 am = None
                 if ctx.f16:
-                    g_am = conv3d._get_amax(gy)
-                    am = (g_am if g_am is not None else conv3d._get_amax(gr), ctx.x_amax)
+                    g_am = _get_amax(gy)
+                    am = (g_am if g_am is not None else _get_amax(gr), ctx.x_amax)
                 gw = _wgrad(gr, xr, cout, cin, cout, cin, kh, kw, dil, sink=ctx.sink, amax=am)
         return gx, gw, None, None, None, None, None
 
@@ -435,7 +404,7 @@ class _ConvS2Patches(torch.autograd.Function):
             _call("az_im2col_s2k3", _p(patches), _p(xr), b, cin, h, w, kp, _stream())
             pk = _pack(w2, kp, cout, 9 * cin, cout, 9 * cin, 1, 1, 1, False)
             if stats is not None and b % stats.groups == 0:
-                y = _run_stats(patches, pk, kp, cout, 1, 1, 1, stats)
+                y = _run(patches, pk, kp, cout, 1, 1, 1, stats=stats)
             else:
                 y = _run(patches, pk, kp, cout, 1, 1, 1, tag="fe2d_first")
         ctx.save_for_backward(patches, w2)

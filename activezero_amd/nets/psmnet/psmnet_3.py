@@ -15,7 +15,7 @@ hard-codes .cuda(); this path has no CPU fallback).
 import math
 
 from activezero_amd import overlap
-from activezero_amd import agg3d, conv3d, ops
+from activezero_amd import agg3d, amax, conv3d, ops, packing
 from activezero_amd.nets.psmnet.psmnet_submodule_3 import *  # noqa: F401,F403
 from activezero_amd.nets.psmnet import psmnet_submodule_3 as _sub
 
@@ -147,8 +147,8 @@ class PSMNet(nn.Module):
             # (the gated aliases of a training pass share storage and version counter with the parameters)
             ws = overlap.conv_weights(self)
             if torch.is_grad_enabled():
-                conv3d.prepack(ws)  # ... and every packed image the last step asked for, in one more launch (conv3d.PackPlan)
-            conv3d.prime_weight_amax(ws)
+                packing.prepack(ws)  # ... and every packed image the last step asked for, in one more launch (packing.PackPlan)
+            amax.prime_weight_amax(ws)
         return self.arith._replace(sink=sink)
 
     def _from_features(self, feat_l, feat_r, arith=None):

@@ -28,8 +28,8 @@ import weakref
 import torch
 import torch.nn as nn
 
-from activezero_amd import _lib, conv2d, conv3d, profiler
-from activezero_amd.conv3d import _CACHE_LOCK, _cache_get, _cache_key, _cache_put
+from activezero_amd import _lib, amax, conv2d, profiler
+from activezero_amd.packing import CACHE_LOCK, cache_get, cache_key, cache_put, memo
 from activezero_amd.ops import _call, _chk, _p, _stream
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, ACT_GRU = range(5)
@@ -46,18 +46,18 @@ def _context_rows(cz, cr, cq):
     it neither keeps the step's autograd graph alive nor answers for a recycled address, and entries whose sources have
     died are dropped at the next conversion."""
     global CTX_CONVERSIONS
-    key = _cache_key(cz, cr, cq)
-    hit = _cache_get(_CTX_CACHE, key)
+    key = cache_key(cz, cr, cq)
+    hit = cache_get(_CTX_CACHE, key)
     if hit is not None and all(r() is t for r, t in zip(hit[1], (cz, cr, cq))):
         return hit[0]
     with torch.no_grad():
         czr = torch.cat([cz.detach().permute(0, 2, 3, 1), cr.detach().permute(0, 2, 3, 1)], -1).float().contiguous()
         cqr = _rows(cq.detach())
     CTX_CONVERSIONS += 1
-    with _CACHE_LOCK:
+    with CACHE_LOCK:
         for k in [k for k, v in _CTX_CACHE.items() if any(r() is None for r in v[1])]:
             del _CTX_CACHE[k]
-    _cache_put(_CTX_CACHE, key, ((czr, cqr), tuple(weakref.ref(t) for t in (cz, cr, cq))), 4)
+    cache_put(_CTX_CACHE, key, ((czr, cqr), tuple(weakref.ref(t) for t in (cz, cr, cq))), 4)
     return czr, cqr
 
 
@@ -73,17 +73,17 @@ def _cached_rows(t):
     """a channels-last fp32 copy of an NCHW tensor that comes back update after update (the context features: the same tensor
     in all 22 updates of a step), made once; weak-referenced like _context_rows' entries"""
     global ROW_CONVERSIONS
-    key = _cache_key(t)
-    hit = _cache_get(_ROWS_CACHE, key)
+    key = cache_key(t)
+    hit = cache_get(_ROWS_CACHE, key)
     if hit is not None and hit[1]() is t:
         return hit[0]
     with torch.no_grad():
         r = t.detach().permute(0, 2, 3, 1).float().contiguous()
     ROW_CONVERSIONS += 1
-    with _CACHE_LOCK:
+    with CACHE_LOCK:
         for k in [k for k, v in _ROWS_CACHE.items() if v[1]() is None]:
             del _ROWS_CACHE[k]
-    _cache_put(_ROWS_CACHE, key, (r, weakref.ref(t)), 8)
+    cache_put(_ROWS_CACHE, key, (r, weakref.ref(t)), 8)
     return r
 
 
@@ -98,10 +98,10 @@ def _source(t):
         return None
     if t.shape[1] <= 128:
         # an image the kernel can transpose on the way -- unless it is the same tensor as last time: then a cached copy is cheaper
-        key = _cache_key(t)
-        seen = _cache_get(_SEEN_ONCE, key)
-        if (seen is None or seen[0]() is not t) and _cache_get(_ROWS_CACHE, key) is None:
-            _cache_put(_SEEN_ONCE, key, (weakref.ref(t),), 8)
+        key = cache_key(t)
+        seen = cache_get(_SEEN_ONCE, key)
+        if (seen is None or seen[0]() is not t) and cache_get(_ROWS_CACHE, key) is None:
+            cache_put(_SEEN_ONCE, key, (weakref.ref(t),), 8)
             return t, 1
     return _cached_rows(t), 0
 
@@ -129,21 +129,16 @@ def _assemble(h, xs):
 
 def _pack_bf16(weights, cache):
     """[Cout_i, Cin, 3, 3] weights (concatenated along Cout) -> the kernel's one-part bf16 image."""
-    key = None
-    if cache:
-        key = _cache_key(*weights)
-        hit = _cache_get(_PACK_CACHE, key)
-        if hit is not None:
-            return hit[0]
-    w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
-    cout, cin, kh, kw = w.shape
-    if _lib.lib().az_conv2d_packed_floats(cin, cout, kh, kw) < 0:
-        raise RuntimeError(f"ConvGRU: unsupported channel counts cin={cin} cout={cout} (need cin % 16 == 0, cout % 32 == 0)")
-    packed = torch.empty(kh * kw * cin * cout // 2, dtype=torch.float32, device=w.device)
-    _call("az_conv2d_pack_weights_bf16", _p(packed), _p(w), cin, cout, cin * kh * kw, kh * kw, kh, kw, _stream())
-    if key is not None:
-        _cache_put(_PACK_CACHE, key, (packed, weights), 64)
-    return packed
+    def make():
+        w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
+        cout, cin, kh, kw = w.shape
+        if _lib.lib().az_conv2d_packed_floats(cin, cout, kh, kw) < 0:
+            raise RuntimeError(f"ConvGRU: unsupported channel counts cin={cin} cout={cout} (need cin % 16 == 0, cout % 32 == 0)")
+        packed = torch.empty(kh * kw * cin * cout // 2, dtype=torch.float32, device=w.device)
+        _call("az_conv2d_pack_weights_bf16", _p(packed), _p(w), cin, cout, cin * kh * kw, kh * kw, kh, kw, _stream())
+        return packed
+
+    return memo(_PACK_CACHE, cache_key(*weights) if cache else None, make, (weights,), 64)
 
 
 def conv3x3_bf16(xr, packed, cin, cout, bias=None, residual=None, act=ACT_NONE, gate_z=None, gate_h=None, h1=False,
@@ -167,22 +162,17 @@ def conv3x3_bf16(xr, packed, cin, cout, bias=None, residual=None, act=ACT_NONE, 
 def _pack_h1(weights, flipped, cache=True):
     """one-part FP16 image (forward, or the input gradient's with flipped = True) of [Cout_i, Cin, 3, 3] weights
     concatenated along Cout; unscaled, as autocast casts them"""
-    key = None
-    if cache:
-        key = ("h1", bool(flipped)) + _cache_key(*weights)
-        hit = _cache_get(_PACK_CACHE, key)
-        if hit is not None:
-            return hit[0]
-    w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
-    cout, cin = w.shape[0], w.shape[1]
-    packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=w.device)
-    if flipped:
-        _call("az_conv2d_pack_weights_h1", _p(packed), _p(w), None, cout, cin, 9, cin * 9, 1, _stream())
-    else:
-        _call("az_conv2d_pack_weights_h1", _p(packed), _p(w), None, cin, cout, cin * 9, 9, 0, _stream())
-    if key is not None:
-        _cache_put(_PACK_CACHE, key, (packed, weights), 64)
-    return packed
+    def make():
+        w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
+        cout, cin = w.shape[0], w.shape[1]
+        packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=w.device)
+        if flipped:
+            _call("az_conv2d_pack_weights_h1", _p(packed), _p(w), None, cout, cin, 9, cin * 9, 1, _stream())
+        else:
+            _call("az_conv2d_pack_weights_h1", _p(packed), _p(w), None, cin, cout, cin * 9, 9, 0, _stream())
+        return packed
+
+    return memo(_PACK_CACHE, ("h1", bool(flipped)) + cache_key(*weights) if cache else None, make, (weights,), 64)
 
 
 def _rows(t):
@@ -233,19 +223,14 @@ class _Conv3x3Bf16(torch.autograd.Function):
 
 def _pack_bf16_flipped(weights, cache):
     """the one-part bf16 image of the INPUT-gradient convolution of [Cout_i, Cin, 3, 3] weights (concatenated along Cout)"""
-    key = None
-    if cache:
-        key = ("flip",) + _cache_key(*weights)
-        hit = _cache_get(_PACK_CACHE, key)
-        if hit is not None:
-            return hit[0]
-    w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
-    cout, cin = w.shape[0], w.shape[1]
-    packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=w.device)
-    _call("az_conv2d_pack_weights_bf16_flipped", _p(packed), _p(w), cout, cin, 9, cin * 9, 3, 3, _stream())
-    if key is not None:
-        _cache_put(_PACK_CACHE, key, (packed, weights), 64)
-    return packed
+    def make():
+        w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
+        cout, cin = w.shape[0], w.shape[1]
+        packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=w.device)
+        _call("az_conv2d_pack_weights_bf16_flipped", _p(packed), _p(w), cout, cin, 9, cin * 9, 3, 3, _stream())
+        return packed
+
+    return memo(_PACK_CACHE, ("flip",) + cache_key(*weights) if cache else None, make, (weights,), 64)
 
 
 class _GRUStepBf16(torch.autograd.Function):
@@ -302,8 +287,8 @@ class _GRUStepBf16(torch.autograd.Function):
             h1 = ctx.h1
             # f16x1: the gradient operands are scaled by a power of two from their amax (taken by the gate kernels that write
             # them) before the fp16 rounding -- the job GradScaler does for the reference (train.py:303-309)
-            am_q = conv3d._ZEROS.take(q) if h1 else None
-            am_z = conv3d._ZEROS.take(q) if h1 else None
+            am_q = amax.ZEROS.take(q) if h1 else None
+            am_z = amax.ZEROS.take(q) if h1 else None
             pkf = (lambda ws: _pack_h1(ws, True)) if h1 else (lambda ws: _pack_bf16_flipped(ws, True))
             _call("az_gru_bwd1", _p(dq), _p(dzr), _p(dh_acc), _p(g), _p(zr), _p(q), _p(hx), npix, c, ci, _p(am_q), _p(am_z), _stream())
             d_rhx = conv3x3_bf16(dq, pkf((wq,)), c, ct, h1=h1, in_amax=am_q)

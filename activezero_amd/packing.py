@@ -1,0 +1,261 @@
+"""Weight images: the memo of packed weights between no_grad forwards and the per-step pack plan of the f16x3 kernels.
+
+The kernels read weights from packed images, not from PyTorch's layouts.  This module owns how an image is reused:
+  * memo(): the inference-time memo the packers of conv3d.py, conv2d.py and nets/raft/gru.py go through, with the key
+    rule (cache_key), the lock and touched(), which tells the version counters in those keys about raw-pointer writes;
+  * PackPlan / prepack / planned_pack: during training, every f16x3 image of a model's parameters in one launch per
+    optimizer step, into persistent buffers.
+"""
+import os
+import threading
+
+import torch
+
+from . import amax
+from .amax import AMAX_SLOTS
+from .ops import _call, _p, _stream
+
+# Inference-time memo of packed weights and folded BatchNorm affine maps (pure functions of parameters
+# that do not change between no_grad forwards).  Whether a call may use it is decided by the CALLER
+# (`cache=` = "autograd is off at the call site", conv3d.conv_bn / conv2d.conv_bn_eval), never inside an autograd
+# Function.  Keys hold the tensors' storage address AND version counter, so an optimizer step or a
+# load_state_dict (both write in place) invalidates them; a BatchNorm's key also holds
+# num_batches_tracked, because this library's own train kernels update running_mean / running_var
+# through raw pointers, which no version counter sees.  Each entry keeps its source tensors alive, so
+# their addresses cannot be recycled for other data.  A lock makes the dicts safe under the threads of
+# nn.DataParallel (train.py:540-541).
+PACK_CACHE, AFFINE_CACHE = {}, {}
+CACHE_LOCK = threading.Lock()
+
+
+def cache_key(*tensors):
+    return tuple((t.data_ptr(), t._version, t.device.index) for t in tensors if t is not None)
+
+
+def cache_get(cache, key):
+    with CACHE_LOCK:
+        return cache.get(key)
+
+
+def cache_put(cache, key, value, limit):
+    with CACHE_LOCK:
+        if len(cache) > limit:
+            cache.clear()
+        cache[key] = value
+
+
+def memo(cache, key, make, keep, limit):
+    """make()'s value, remembered in `cache` under `key` (None: not memoised, the call site has autograd on) together with
+    the source tensors `keep`; a cache that has grown past `limit` entries is emptied"""
+    if key is None:
+        return make()
+    hit = cache_get(cache, key)
+    if hit is not None:
+        return hit[0]
+    value = make()
+    cache_put(cache, key, (value,) + tuple(keep), limit)
+    return value
+
+
+def touched(*tensors):
+    """Bump the version counters of buffers a kernel has just written through their raw pointers (BatchNorm
+    running statistics and call counter): the memoised inference operands are keyed on them."""
+    for t in tensors:
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
+
+
+# ---- pack plan (round 5): every f16x3 weight image of a model in ONE launch per optimizer step ----------------------------
+# A training step used to pack each convolution weight twice (forward image, flipped / swapped input-gradient image), one
+# launch and one allocation each: ~175 launches of ~4 us per step on the main stream.  The plan remembers, per device, which
+# images the registered parameters were asked for (recorded by the first step's per-call packs), keeps ONE persistent buffer
+# per image and a descriptor table on the device, and `prepack` rewrites all of them with az_pack_f16_multi when the
+# parameters' version counters have moved.  _pack_f16 (conv3d.py, conv2d.py) then returns the plan's buffer.
+#   * persistent buffers are safe in stream order: only main-stream kernels (forward, input gradient) read packed images,
+#     and the next step's prepack is enqueued behind them on the same stream;
+#   * only tensors registered through prepack() -- live nn.Parameters, held by weak reference -- have entries: derived
+#     weights (the merged kernels of K3', DataParallel replicas) change address every step and keep the per-call route;
+#   * an entry is valid for one (address, version counter): optimizer steps and load_state_dict write in place and bump it.
+PACK_2D_SAME, PACK_2D_ROLL, PACK_3D_GATHER, PACK_3D_ROLL, PACK_3D_ROLL2 = 0, 1, 2, 3, 4
+_PLAN_ON = os.environ.get("AZ_PACK_PLAN", "1") != "0"  # (read once) 0: every image packed by its own launch, as in round 4
+
+
+class _PackEntry:
+    __slots__ = ("wref", "kind", "cin", "cout", "ci_real", "co_real", "s_co", "s_ci", "taps", "flip", "packed", "amax",
+                 "version", "index")
+
+
+class PackPlan:
+    """the images of one device"""
+    DESC_BYTES = 72  # sizeof(AzPackDesc): 3 pointers, 2 long long, 8 ints
+
+    def __init__(self, device):
+        self.device = device
+        self.lock = threading.RLock()
+        self.registered = {}   # data_ptr -> weakref of the parameter
+        self.entries = {}      # (data_ptr, kind, cin, cout, ci_real, co_real, s_co, s_ci, taps, flip) -> _PackEntry
+        self.amax_rows = {}    # data_ptr -> (row tensor [AMAX_SLOTS], weakref)
+        self.amax_blocks = []  # [tensor [256, AMAX_SLOTS], next row]
+        self.table = None      # (descs, block_desc, first_block, nd, nblocks, entry list) on the device: the last one used
+        self.tables = {}       # tuple of registered addresses -> table + the amax pointers it was built with
+        self.launches = 0      # az_pack_f16_multi launches so far (tests)
+
+    # -- weight amax rows: persistent, so that the descriptor table stays valid across steps
+    def amax_row(self, w):
+        ptr = w.data_ptr()
+        hit = self.amax_rows.get(ptr)
+        if hit is not None and hit[1]() is not None:
+            return hit[0]
+        if not self.amax_blocks or self.amax_blocks[-1][1] >= self.amax_blocks[-1][0].shape[0]:
+            self.amax_blocks.append([torch.zeros(256, AMAX_SLOTS, dtype=torch.float32, device=self.device), 0])
+        blk = self.amax_blocks[-1]
+        row = blk[0][blk[1]]
+        blk[1] += 1
+        return row
+
+    def alive(self, ptr):
+        r = self.registered.get(ptr)
+        return r is not None and r() is not None
+
+    def purge(self):
+        dead = [p for p, r in self.registered.items() if r() is None]
+        if dead:
+            dead = set(dead)
+            for p in dead:
+                del self.registered[p]
+                self.amax_rows.pop(p, None)
+            self.entries = {k: e for k, e in self.entries.items() if k[0] not in dead}
+            self.table = None
+            self.tables.clear()
+
+    def lookup(self, weight, kind, cin, cout, ci_real, co_real, s_co, s_ci, taps, flip):
+        """(entry, fresh): the entry of this image of a registered live parameter (created on first request), and whether its
+        buffer already holds the image of the parameter's current version; None for unregistered tensors"""
+        ptr = weight.data_ptr()
+        with self.lock:
+            if not self.alive(ptr):
+                return None, False
+            key = (ptr, kind, cin, cout, ci_real, co_real, int(s_co), int(s_ci), taps, bool(flip))
+            e = self.entries.get(key)
+            if e is None:
+                e = _PackEntry()
+                e.wref, e.kind, e.cin, e.cout, e.ci_real, e.co_real = self.registered[ptr], kind, cin, cout, ci_real, co_real
+                e.s_co, e.s_ci, e.taps, e.flip = int(s_co), int(s_ci), taps, bool(flip)
+                e.packed = torch.empty(taps * cin * cout, dtype=torch.float32, device=self.device)  # two fp16 parts per weight
+                e.amax, e.version = None, -1
+                self.entries[key] = e
+                self.table = None  # rebuilt at the next prepack
+                self.tables.clear()
+            return e, e.version == weight._version
+
+    def _build_table(self, todo):
+        import numpy as np
+        nd = len(todo)
+        raw = np.zeros(nd * self.DESC_BYTES, dtype=np.uint8)
+        q = raw.view(np.int64).reshape(nd, self.DESC_BYTES // 8)
+        ints = raw.view(np.int32).reshape(nd, self.DESC_BYTES // 4)
+        block_desc, first = [], []
+        nblocks = 0
+        for i, e in enumerate(todo):
+            w = e.wref()
+            q[i, 0], q[i, 1], q[i, 2] = e.packed.data_ptr(), w.data_ptr(), e.amax.data_ptr()
+            q[i, 3], q[i, 4] = e.s_co, e.s_ci
+            ints[i, 10:17] = (e.kind, e.cin, e.cout, e.ci_real, e.co_real, e.taps, int(e.flip))
+            nb = (2 * e.taps * e.cin * e.cout + 255) // 256
+            first.append(nblocks)
+            block_desc.append(np.full(nb, i, dtype=np.int32))
+            nblocks += nb
+        dev = self.device
+        self.table = (torch.from_numpy(raw).to(dev), torch.from_numpy(np.concatenate(block_desc)).to(dev),
+                      torch.tensor(first, dtype=torch.int32, device=dev), nd, nblocks, list(todo))
+
+    def prepack(self, weights):
+        """register `weights` (nn.Parameters) and bring every recorded image of THEIRS up to their current version in one
+        launch (a table per set of weights: another live model's images are not this call's business); the amax arrays of
+        all of them in three launches (as prime_weight_amax)"""
+        with self.lock:
+            self.purge()
+            import weakref
+            mine = []
+            for w in weights:
+                if w is None or not w.is_cuda or w.dtype != torch.float32 or w.device != self.device:
+                    continue
+                r = self.registered.get(w.data_ptr())
+                if r is None or r() is not w:
+                    self.registered[w.data_ptr()] = weakref.ref(w)
+                mine.append(w.data_ptr())
+            setkey = tuple(sorted(set(mine)))
+            owned = set(setkey)
+            todo = [e for k, e in self.entries.items() if k[0] in owned and e.wref() is not None]
+            stale = [e for e in todo if e.version != e.wref()._version]
+            if not stale:
+                return
+            with torch.no_grad(), torch.cuda.device(self.device):
+                # amax rows of the weights behind the stale images (persistent rows: slot 0 rewritten in place)
+                ws = {}
+                for e in stale:
+                    w = e.wref()
+                    ws[w.data_ptr()] = w
+                wl = list(ws.values())
+                rows = []
+                for w in wl:
+                    row = self.amax_row(w)
+                    self.amax_rows[w.data_ptr()] = (row, self.registered[w.data_ptr()])
+                    rows.append(row)
+                maxes = torch._foreach_norm([w.detach() for w in wl], float("inf"))
+                torch._foreach_copy_([r[0:1] for r in rows], [m.reshape(1) for m in maxes])
+                for w, row in zip(wl, rows):
+                    amax.remember_weight_amax(w, row)
+                for e in stale:
+                    e.amax = self.amax_rows[e.wref().data_ptr()][0]
+                todo = [e for e in todo if e.amax is not None]
+                tab = self.tables.get(setkey)
+                if tab is None or tab[5] != todo or any(e.amax.data_ptr() != p for e, p in zip(todo, tab[6])):
+                    self._build_table(todo)
+                    tab = self.table + ([e.amax.data_ptr() for e in todo],)
+                    if len(self.tables) > 8:
+                        self.tables.clear()
+                    self.tables[setkey] = tab
+                descs, block_desc, first, nd, nblocks, elist, _ = tab
+                _call("az_pack_f16_multi", _p(descs), _p(block_desc), _p(first), nd, nblocks, _stream())
+                self.launches += 1
+                for e in elist:
+                    e.version = e.wref()._version
+                self.table = tab[:6]  # (the last table used: tests read it)
+
+
+_PLANS = {}
+
+
+def pack_plan(device):
+    with CACHE_LOCK:
+        p = _PLANS.get(device)
+        if p is None:
+            p = _PLANS[device] = PackPlan(device)
+        return p
+
+
+def prepack(weights):
+    """start of a training forward pass: all f16x3 images of these parameters in one launch (PackPlan)"""
+    ws = [w for w in weights if w is not None and w.is_cuda]
+    if _PLAN_ON and ws:
+        pack_plan(ws[0].device).prepack(ws)
+
+
+def planned_pack(weight, w, kind, cin, cout, ci_real, co_real, s_co, s_ci, taps, flip, pack_now):
+    """the plan's (buffer, amax) for this image of a registered parameter, packed by `pack_now(packed, w_amax)` -- the
+    per-tensor launch -- when the plan has not brought it up to date (first step, or no prepack this step); None for tensors
+    the plan does not own"""
+    if not _PLAN_ON or not w.is_cuda:
+        return None
+    plan = pack_plan(w.device)
+    e, fresh = plan.lookup(weight, kind, cin, cout, ci_real, co_real, s_co, s_ci, taps, flip)
+    if e is None:
+        return None
+    if not fresh:
+        with plan.lock:
+            w_amax = amax.weight_amax(weight, w)
+            pack_now(e.packed, w_amax)
+            e.amax, e.version = w_amax, weight._version
+            # (this entry's amax pointer may have changed: prepack compares the pointers its table was built with)
+    return e.packed, e.amax

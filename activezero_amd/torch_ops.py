@@ -205,7 +205,7 @@ _LIB.define("patch_reproj_bwd(Tensor grad_loss, Tensor left, Tensor right, Tenso
 
 
 def _c3_channels(weight, mode):
-    return (weight.shape[0], weight.shape[1]) if mode == _c3.DECONV_S2 else (weight.shape[1], weight.shape[0])
+    return _c3._fwd_launch(weight, mode)[:2]
 
 
 def _conv3d(x, weight, mode):

@@ -8,7 +8,8 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from activezero_amd import agg3d, conv3d, ops  # noqa: E402
+from activezero_amd import agg3d, amax, conv3d, ops  # noqa: E402
+from activezero_amd import handover as handover_mod  # noqa: E402
 from activezero_amd.nets.psmnet import psmnet_3  # noqa: E402
 from oracle import psmnet_oracle as po  # noqa: E402
 from tests._weights import load_procedural, seeded  # noqa: E402
@@ -307,7 +308,7 @@ def test_bn_backward_presplit_output_is_the_split_of_the_fp32_one(c, shape, relu
         ws = torch.empty(wsb // 4, device=DEV)
         dx = torch.empty_like(raw)
         dg, db, coef = torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty(c, 3, device=DEV)
-        am = torch.full((conv3d.AMAX_SLOTS,), 7.0, device=DEV)  # (need not be zero: the first kernel clears it)
+        am = torch.full((amax.AMAX_SLOTS,), 7.0, device=DEV)  # (need not be zero: the first kernel clears it)
         _call("az_bn3d_bwd", _p(dx), None, _p(dg), _p(db), _p(coef), _p(ws), wsb, _p(gy), None, _p(raw), _p(mean), _p(invstd),
               _p(gamma), _p(scale) if relu else None, _p(shift) if relu else None, int(relu), nvox, c, _p(am), split, _stream())
         out[split] = (dx, am, dg, db)
@@ -329,10 +330,10 @@ def test_bn_backward_presplit_output_is_the_split_of_the_fp32_one(c, shape, relu
     if c == 32:
         wt = (seeded((c, c, 3, 3, 3), 65) * 0.1).to(DEV)
         dxs = out[1][0]
-        conv3d._set_amax(dxs, out[1][1])
+        amax._set_amax(dxs, out[1][1])
         dxs.az_split = True
         dec = got.float().to(DEV)
-        conv3d._set_amax(dec, out[1][1])  # the same scale: the same two fp16 parts
+        amax._set_amax(dec, out[1][1])  # the same scale: the same two fp16 parts
         with torch.no_grad():
             a = conv3d._input_grad(dxs, wt, conv3d.CONV_S1, c, c, conv3d.F16X3)
             bb = conv3d._input_grad(dec, wt, conv3d.CONV_S1, c, c, conv3d.F16X3)
@@ -364,7 +365,7 @@ def test_presplit_routing_matches_the_library_queries():
     assert not ok(t(64, 2, 4, 8), t(64, 4, 8, 16), conv3d.DECONV_S2, 64, 64, True, True)     # conv5: gather kernel
 
 
-# ---- round 5: gradient hand-over between the consumers of one tensor (conv3d.GradSlot) -----------------------------------
+# ---- round 5: gradient hand-over between the consumers of one tensor (handover.GradSlot) -----------------------------------
 def _fork_net(x, units, arith):
     """y = unit_a(t) + relu-free residual(t), t = unit0(x): t has two consumers inside one _ConvBN (x and residual of different
     nodes) and a third one through a second branch -- the shapes of the hourglass skips"""
@@ -383,7 +384,7 @@ def test_gradient_handover_equals_the_engines_sum(use, monkeypatch):
     cv, cw = cl(seeded((1, 32, 4, 8, 16), 22)), cl(seeded((1, 32, 4, 8, 16), 23))
 
     def run(handover):
-        monkeypatch.setattr(conv3d, "_HANDOVER", handover)
+        monkeypatch.setattr(handover_mod, "_HANDOVER", handover)
         for u in units:
             u.zero_grad(set_to_none=True)
         x = cl(x0).requires_grad_()

@@ -17,7 +17,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from activezero_amd import _lib, conv3d, overlap  # noqa: E402
+from activezero_amd import _lib, amax, conv3d, overlap  # noqa: E402
 from activezero_amd.ops import _call, _p, _stream  # noqa: E402
 from tests import _fp64ref as R  # noqa: E402
 from tests._weights import seeded  # noqa: E402
@@ -240,11 +240,11 @@ def presplit(t_cl, seed):
     for split in (1, 0):
         ws, dx = torch.empty(wsb // 4, device=DEV), torch.empty_like(t_cl)
         small = [torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty(c, 3, device=DEV)]
-        am = torch.zeros(conv3d.AMAX_SLOTS, device=DEV)
+        am = torch.zeros(amax.AMAX_SLOTS, device=DEV)
         _call("az_bn3d_bwd", _p(dx), None, _p(small[0]), _p(small[1]), _p(small[2]), _p(ws), wsb, _p(t_cl), None, _p(raw),
               _p(v[0]), _p(v[1]), _p(v[2]), None, None, 0, nv, c, _p(am), split, _stream())
         if split:
-            conv3d._set_amax(dx, am)
+            amax._set_amax(dx, am)
             dx.az_split = True
         outs.append(dx)
     return outs
@@ -252,7 +252,7 @@ def presplit(t_cl, seed):
 
 def decoded_parts(t):
     """a pre-split tensor -> its [hi, lo] parts (NCDHW fp64, unscaled) and the amax bound they were scaled by"""
-    a = float(conv3d._get_amax(t)[::64].max())
+    a = float(amax._get_amax(t)[::64].max())
     k = R.f16_scale_exp(a)
     f = t.contiguous().view(torch.int16).view(-1, 8).view(torch.float16).double().cpu()
     hi, lo = (f[:, :4].reshape(t.shape), f[:, 4:].reshape(t.shape))
@@ -335,7 +335,7 @@ def test_accumulate_only_into_one_arena_then_unpack(capsys):
         b, d, h, w = shape
         x, wt, dy = operands(ci, co, shape)
         xg, dg = cl(x), cl(dy)
-        am_x, am_dy = conv3d.absmax(xg), conv3d.absmax(dg)
+        am_x, am_dy = amax.absmax(xg), amax.absmax(dg)
         ws = arena[off:off + n]
         off += n
         gw = torch.full((co, ci, 3, 3, 3), float("nan"), device=DEV)

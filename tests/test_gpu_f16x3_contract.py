@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from activezero_amd import conv3d  # noqa: E402
+from activezero_amd import amax, conv3d  # noqa: E402
 from tests._weights import seeded  # noqa: E402
 
 DEV = "cuda:0"
@@ -37,7 +37,7 @@ def ncdhw(x):
 
 
 def amax_array(value):
-    am = torch.zeros(conv3d.AMAX_SLOTS, device=DEV)
+    am = torch.zeros(amax.AMAX_SLOTS, device=DEV)
     am[0] = value
     return am
 
@@ -47,9 +47,9 @@ def run(kind, x, wt, dy, amax_x=None, amax_dy=None):
     c = wt.shape[0]
     xg, dg, wg = cl(x), cl(dy), wt.to(DEV)
     if amax_x is not None:
-        conv3d._set_amax(xg, amax_array(amax_x))
+        amax._set_amax(xg, amax_array(amax_x))
     if amax_dy is not None:
-        conv3d._set_amax(dg, amax_array(amax_dy))
+        amax._set_amax(dg, amax_array(amax_dy))
     with torch.no_grad():
         if kind == "fwd":
             return ncdhw(conv3d._conv(xg, wg, conv3d.CONV_S1, conv3d.F16X3))
@@ -199,12 +199,12 @@ def test_a_stale_too_small_amax_overflows_loudly(c, dims, kind):
 
 def test_debug_amax_check_names_a_stale_attribute():
     x = cl(seeded((1, 32, 4, 8, 16), 4600))
-    conv3d._set_amax(x, amax_array(float(x.abs().max()) / 8))
+    amax._set_amax(x, amax_array(float(x.abs().max()) / 8))
     with pytest.raises(RuntimeError, match="stale amax"):
-        conv3d.check_amax(x, conv3d._get_amax(x))
-    conv3d._set_amax(x, amax_array(float(x.abs().max()) * 2))
-    conv3d.check_amax(x, conv3d._get_amax(x))  # a loose bound is legal
+        amax.check_amax(x, amax._get_amax(x))
+    amax._set_amax(x, amax_array(float(x.abs().max()) * 2))
+    amax.check_amax(x, amax._get_amax(x))  # a loose bound is legal
     # the kernels' own producers: BatchNorm apply writes max |y| of what it stores
     y = conv3d.add(x, x)
-    conv3d.check_amax(y, conv3d._get_amax(y))
-    assert abs(float(conv3d._get_amax(y)[::64].max()) - float(y.abs().max())) == 0.0
+    amax.check_amax(y, amax._get_amax(y))
+    assert abs(float(amax._get_amax(y)[::64].max()) - float(y.abs().max())) == 0.0

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from activezero_amd import _lib, conv3d  # noqa: E402
+from activezero_amd import _lib, conv3d, packing  # noqa: E402
 from activezero_amd.ops import _call, _p, _stream  # noqa: E402
 from tests.test_gpu_s2roll import _presplit, cl, ncdhw, seeded  # noqa: E402
 
@@ -29,9 +29,9 @@ def test_routing_and_layout():
     lib = _lib.lib()
     if not on_roll64():
         pytest.skip("AZ_CONV_ROLL64=0")
-    assert lib.az_conv3d_f16_layout(conv3d.CONV_S1, 64, 64) == conv3d.PACK_3D_ROLL2
-    assert lib.az_conv3d_f16_layout(conv3d.CONV_S1, 64, 32) == conv3d.PACK_3D_ROLL
-    assert lib.az_conv3d_f16_layout(conv3d.CONV_S1, 32, 64) == conv3d.PACK_3D_GATHER
+    assert lib.az_conv3d_f16_layout(conv3d.CONV_S1, 64, 64) == packing.PACK_3D_ROLL2
+    assert lib.az_conv3d_f16_layout(conv3d.CONV_S1, 64, 32) == packing.PACK_3D_ROLL
+    assert lib.az_conv3d_f16_layout(conv3d.CONV_S1, 32, 64) == packing.PACK_3D_GATHER
     assert lib.az_conv3d_fwd_f16_split_ok(conv3d.CONV_S1, 4, 64, 64, 24, 68, 120) == 1
 
 

@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from activezero_amd import _lib, conv3d  # noqa: E402
+from activezero_amd import _lib, amax, conv3d  # noqa: E402
 from activezero_amd.ops import _call, _p, _stream  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -131,11 +131,11 @@ def _presplit(dy):
     for split in (1, 0):
         ws, dx = torch.empty(wsb // 4, device=DEV), torch.empty_like(dy)
         small = [torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty(c, 3, device=DEV)]
-        am = torch.zeros(conv3d.AMAX_SLOTS, device=DEV)
+        am = torch.zeros(amax.AMAX_SLOTS, device=DEV)
         _call("az_bn3d_bwd", _p(dx), None, _p(small[0]), _p(small[1]), _p(small[2]), _p(ws), wsb, _p(dy), None, _p(raw), _p(v[0]),
               _p(v[1]), _p(v[2]), None, None, 0, nv, c, _p(am), split, _stream())
         if split:
-            conv3d._set_amax(dx, am)
+            amax._set_amax(dx, am)
             dx.az_split = True
         outs.append(dx)
     return outs

@@ -5,7 +5,7 @@ V1 -> V0), the 64 -> 64 layers at V1 / V2 -- in the default arithmetic (f16x3) a
 respective roofline (fp32-equivalent: 2500 / 3 and 2500 / 6 TFLOP/s).  VERDICT r3 item 1's table."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from activezero_amd import conv3d
+from activezero_amd import amax, conv3d
 dev = torch.device("cuda:0")
 B = 4
 q, e, s16 = (48, 136, 240), (24, 68, 120), (12, 34, 60)
@@ -36,10 +36,10 @@ def presplit(dy):
     ws, dx = torch.empty(wsb // 4, device=dev), torch.empty_like(dy)
     v = [torch.zeros(c, device=dev), torch.ones(c, device=dev), torch.ones(c, device=dev)]
     small = [torch.empty(c, device=dev), torch.empty(c, device=dev), torch.empty(c, 3, device=dev)]
-    am = torch.zeros(conv3d.AMAX_SLOTS, device=dev)
+    am = torch.zeros(amax.AMAX_SLOTS, device=dev)
     _call("az_bn3d_bwd", _p(dx), None, _p(small[0]), _p(small[1]), _p(small[2]), _p(ws), wsb, _p(dy), None, _p(raw), _p(v[0]), _p(v[1]),
           _p(v[2]), None, None, 0, nv, c, _p(am), 1, _stream())
-    conv3d._set_amax(dx, am)
+    amax._set_amax(dx, am)
     dx.az_split = True
     return dx
 

@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from activezero_amd import conv3d  # noqa: E402
+from activezero_amd import amax, conv3d  # noqa: E402
 
 dev = torch.device("cuda:0")
 torch.manual_seed(4)
@@ -52,7 +52,7 @@ for name, cout, cin, gscale, tail, wscale in (
     dyg, wg = dy.to(dev), w.to(dev)
     pk = conv3d._pack(wg, cout, cin, 27, cin * 27, True, conv3d._layout(conv3d.BF16X6, conv3d.CONV_S1, cin))
     x6 = conv3d._run_gather(dyg, pk, conv3d.CONV_S1, cout, cin, conv3d.BF16X6, tag="dgrad")
-    h3 = conv3d._input_grad_f16(dyg, wg, conv3d.CONV_S1, cin, cout)
+    h3 = conv3d._input_grad(dyg, wg, conv3d.CONV_S1, cin, cout, conv3d.F16X3)
     dyg.az_amax = None  # (the next case is a new tensor anyway)
     cells = ["%.2e / %.2e (%+.1e)" % err(v, ref) for v in (x6, h3, t32)]
     print(f"{name:46s} {cells[0]:>28s} {cells[1]:>28s} {cells[2]:>28s}")
@@ -66,7 +66,7 @@ g = torch.randn(B, D, H, W, C, device=dev) * 1e-6
 w = torch.randn(C, C, 3, 3, 3, device=dev) * 0.05
 pd = conv3d._pack(w, C, C, 27, C * 27, True, conv3d._layout(conv3d.BF16X6, conv3d.CONV_S1, C))
 pk16, wam = conv3d._pack_f16(w, C, C, 27, C * 27, True, conv3d.CONV_S1)
-gam = conv3d.absmax(g)
+gam = amax.absmax(g)
 out = torch.empty_like(g)
 from activezero_amd.ops import _call, _p, _stream  # noqa: E402
 

@@ -17,7 +17,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from activezero_amd import conv3d  # noqa: E402
+from activezero_amd import amax, conv3d  # noqa: E402
 from activezero_amd.ops import _call, _p, _stream  # noqa: E402
 
 B, D, H, W, C = int(os.environ.get("AZ_PROBE_B", 4)), 48, 136, 240, 32
@@ -49,7 +49,7 @@ def main():
         dx = torch.empty_like(x)
         _call("az_bn3d_bwd", _p(dx), None, _p(dgm), _p(dbt), _p(coef), _p(ws), wsb, _p(g), None, _p(x), _p(shift), _p(scale),
               _p(scale), _p(scale), _p(shift), 1, nv, C, _p(am), split, _stream())
-        conv3d._set_amax(dx, am)
+        amax._set_amax(dx, am)
         if split:
             dx.az_split = True
         conv3d._input_grad(dx, w, conv3d.CONV_S1, C, C, conv3d.F16X3 if A.bwd16 else A.conv)

@@ -11,5 +11,5 @@ w = torch.randn(C, C, 3, 3, 3, device=dev) * 0.05
 pd = conv3d._pack(w, C, C, 27, C * 27, True, conv3d._layout(conv3d.BF16X6, conv3d.CONV_S1, C))
 for _ in range(6):
     conv3d._run_gather(g, pd, conv3d.CONV_S1, C, C, conv3d.BF16X6, tag="dgrad")
-    conv3d._input_grad_f16(g, w, conv3d.CONV_S1, C, C)
+    conv3d._input_grad(g, w, conv3d.CONV_S1, C, C, conv3d.F16X3)
 torch.cuda.synchronize()

@@ -3,13 +3,13 @@
 32 -> 32 at 272 x 480 (firstconv / layer1); HIP events over 20 launches behind 10.  AZ_CONV2D_WGRAD_W64 selects the 64 x 64-tile kernel."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from activezero_amd import conv2d, conv3d, _lib
+from activezero_amd import _lib, amax, conv2d
 dev = torch.device("cuda:0")
 print("AZ_CONV2D_WGRAD_W64 =", _lib.lib().az_option(b"AZ_CONV2D_WGRAD_W64"))
 for c, (h, w) in ((64, (136, 240)), (32, (272, 480))):
     xr = torch.randn(8, h, w, c, device=dev).relu_()
     gr = torch.randn(8, h, w, c, device=dev) * 1e-4
-    am = (conv3d.absmax(gr), conv3d.absmax(xr))
+    am = (amax.absmax(gr), amax.absmax(xr))
     f = lambda: conv2d._wgrad(gr, xr, c, c, c, c, 3, 3, 1, amax=am)
     for _ in range(10): f()
     torch.cuda.synchronize()
