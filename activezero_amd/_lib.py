@@ -68,6 +68,11 @@ _SIGS = {
     "az_disp_loss_fwd": [_PTR] * 6 + [_C.c_float, _C.c_float, _C.c_longlong, _PTR],
     "az_disp_loss_bwd": [_PTR] * 8 + [_C.c_float, _C.c_float, _PTR, _PTR] + [_C.c_float] * 3 + [_C.c_longlong, _PTR],
     "az_disp_metrics": [_PTR] * 7 + [_INT, _C.c_longlong, _PTR],
+    "az_convex_up_fwd": [_PTR] * 3 + [_INT] * 9 + [_PTR],
+    "az_convex_up_bwd_workspace": [_INT] * 4,
+    "az_convex_up_bwd": [_PTR] * 3 + [_LL] + [_PTR] * 3 + [_INT] * 9 + [_PTR],
+    "az_seq_loss_fwd": [_PTR] * 4 + [_INT, _C.c_float, _INT, _LL, _PTR],
+    "az_seq_loss_bwd": [_PTR] * 4 + [_INT, _C.c_float, _INT, _PTR, _PTR, _C.c_float, _LL, _PTR],
     "az_conv3d_packed_floats": [_INT, _INT, _INT],
     "az_conv3d_pack_weights": [_PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _INT, _PTR],
     "az_conv3d_num_tiles": [_INT] * 5,
@@ -131,7 +136,8 @@ _RESTYPE = {"az_strerror": _C.c_char_p, "az_conv3d_num_tiles": _LL, "az_conv3d_s
             "az_conv3d_wgrad_workspace": _LL, "az_bn3d_bwd_workspace": _LL, "az_spp_upsample_bwd_workspace": _LL,
             "az_bn3d_stats_tiles": _LL, "az_bn2d_workspace": _LL,
             "az_conv2d_packed_floats": _LL, "az_conv2d_wgrad_workspace": _LL, "az_ir_pattern_workspace": _LL,
-            "az_bn3d_finalize_scratch": _LL, "az_conv2d_stats_tiles": _LL}
+            "az_bn3d_finalize_scratch": _LL, "az_conv2d_stats_tiles": _LL,
+            "az_convex_up_bwd_workspace": _LL}
 
 
 def declared_symbols():

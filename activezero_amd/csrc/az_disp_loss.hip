@@ -6,6 +6,7 @@
 // applied in registers and every sum lands in a small fp64 accumulator vector the caller owns.
 // HBM-bound: 4 maps read per pixel (16 B + mask byte); tiny next to the path itself, the point
 // is the removed syncs and launches.
+#include "az_block_reduce.h"
 #include "az_common.h"
 
 #define DL_BLOCK 256
@@ -14,27 +15,9 @@ __device__ __forceinline__ bool dl_valid(const unsigned char *mask, float gt, fl
     return mask ? (mask[i] != 0) : (gt > lo && gt < hi);
 }
 
-// block reduction (wave shuffles, then LDS across the 4 waves) and ONE fp64 atomic per block and
-// accumulator: with an atomic per wave the 130 k same-address adds of a 4 x 544 x 960 map
-// serialised in L2 and the kernel took 0.79 ms instead of ~15 us
+// block reduction: az_block_reduce.h (shared with K16)
 template <int N>
-__device__ __forceinline__ void dl_flush(double (&v)[N], double *acc) {
-    __shared__ double red[DL_BLOCK / 64][N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double x = v[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        double x = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < DL_BLOCK / 64; ++wv) x += red[wv][threadIdx.x];
-        if (x != 0.0) atomicAdd(&acc[threadIdx.x], x);
-    }
-}
+__device__ __forceinline__ void dl_flush(double (&v)[N], double *acc) { az_block_sum_f64<N, DL_BLOCK>(v, acc); }
 
 // acc[0..2] += sum of smooth_l1(pred3|pred2|pred1 - gt) over valid pixels, acc[3] += count
 __global__ void __launch_bounds__(DL_BLOCK)

@@ -317,3 +317,119 @@ def disp_metrics(disp_gt, depth_gt, disp_pred, mask, focal_x_baseline=None, dept
         _call("az_disp_metrics", _p(acc), _p(dg), _p(zg), _p(dp), _p(zp), _p(fb), _p(m), b,
               dg.numel() // max(b, 1), _stream())
     return acc
+
+
+# ----------------------------------------------------------------------------
+# K15 RAFT-Stereo convex upsampling
+# ----------------------------------------------------------------------------
+def _chk_mask(mask, name="mask"):
+    if isinstance(mask, torch.Tensor) and mask.dtype == torch.float16:
+        return _chk(mask, name, torch.float16)
+    return _chk(mask, name)
+
+
+class _ConvexUp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, mask, factor, d_out, sign):
+        flow = _chk(flow.contiguous(), "flow")
+        mask = _chk_mask(mask.contiguous())
+        if flow.dim() != 4 or mask.dim() != 4:
+            raise RuntimeError("flow must be [N,D,h,w] and mask [N,9*factor*factor,h,w]")
+        n, d, h, w = flow.shape
+        if mask.shape[0] != n or tuple(mask.shape[2:]) != (h, w):
+            raise RuntimeError(f"mask {tuple(mask.shape)} does not match flow {tuple(flow.shape)}")
+        up = flow.new_empty(n, d_out, factor * h, factor * w)
+        ctx.args = (int(mask.dtype == torch.float16), n, d, d_out, h, w, factor, mask.shape[1], sign)
+        with torch.cuda.device(flow.device):
+            _call("az_convex_up_fwd", _p(up), _p(flow), _p(mask), *ctx.args, _stream())
+        ctx.save_for_backward(flow, mask)  # the inputs only: the softmax is recomputed, nothing of mask size is kept
+        return up
+
+    @staticmethod
+    def backward(ctx, g):
+        flow, mask = ctx.saved_tensors
+        g = _chk(g.contiguous(), "grad_up")
+        if g.data_ptr() % 16:  # a contiguous view at an odd storage offset: the kernel reads g_up as float4
+            g = g.clone()
+        _, n, _, d_out, h, w = ctx.args[:6]
+        gm, gf = torch.empty_like(mask), torch.empty_like(flow)
+        nbytes = _lib.lib().az_convex_up_bwd_workspace(n, d_out, h, w)
+        ws = flow.new_empty(nbytes // 4)
+        with torch.cuda.device(flow.device):
+            _call("az_convex_up_bwd", _p(gm), _p(gf), _p(ws), nbytes, _p(g), _p(flow), _p(mask), *ctx.args, _stream())
+        return gf, gm, None, None, None
+
+
+def convex_upsample(flow, mask, factor, channels=None, negate=False):
+    """RAFTStereo.upsample_flow as one kernel: flow [N,D,h,w] fp32, mask [N,9*factor^2,h,w] fp32 or fp16 ->
+    [N,channels,factor*h,factor*w] fp32, the softmax-weighted sum of the 3x3 neighbourhood of factor*flow.
+    channels (default D) < D computes the leading channels only (`flow_up[:, :1]`); negate returns the
+    negated result (`pred_disp = -output[-1]`).  One autograd node; nothing of mask size is saved."""
+    d_out = flow.shape[1] if channels is None else int(channels)
+    return _ConvexUp.apply(flow, mask, int(factor), d_out, -1 if negate else 1)
+
+
+# ----------------------------------------------------------------------------
+# K16 sequence loss
+# ----------------------------------------------------------------------------
+class _SeqLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gt, valid, weights, max_flow, tsign, check, *preds):
+        gt = _chk(gt.contiguous(), "flow_gt")
+        if valid.shape != gt.shape:
+            raise RuntimeError(f"valid: shape {tuple(valid.shape)} != {tuple(gt.shape)}")
+        if valid.dtype == torch.float32:
+            valid = _chk(valid.contiguous(), "valid")
+        else:
+            valid = _mask_u8(valid.contiguous(), gt, "valid")
+        ps = []
+        for i, p in enumerate(preds):
+            p = _chk(p.contiguous(), f"flow_preds[{i}]")
+            if p.shape != gt.shape:
+                raise RuntimeError(f"flow_preds[{i}]: shape {tuple(p.shape)} != {tuple(gt.shape)}")
+            ps.append(p)
+        n = len(ps)
+        acc = torch.zeros(n, 3, dtype=torch.float64, device=gt.device)
+        ctx.args = (int(valid.dtype == torch.uint8), float(max_flow), tsign)
+        with torch.cuda.device(gt.device):
+            for i, p in enumerate(ps):
+                _call("az_seq_loss_fwd", acc.data_ptr() + 24 * i, _p(p), _p(gt), _p(valid), *ctx.args, gt.numel(),
+                      _stream())
+        if check:  # the one host sync, on request: losses.py:53-56 asserts every prediction finite
+            bad = acc[:, 2].tolist()
+            if any(bad):
+                raise AssertionError(f"sequence_loss: non-finite values in flow_preds {[i for i, b in enumerate(bad) if b]}")
+        # w_i from an on-device arange: a host list would be a blocking copy.  0/0 = nan, as the reference's empty mean
+        gp, k = weights
+        wts = torch.pow(gp, (k - torch.arange(n, device=gt.device)).to(torch.float64))
+        loss = (wts * acc[:, 0] / acc[:, 1]).sum().to(torch.float32)
+        ctx.save_for_backward(gt, valid, acc, *ps)
+        ctx.weights = [gp ** (k - i) for i in range(n)]
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        gt, valid, acc, *ps = ctx.saved_tensors
+        gloss = _chk(gloss.contiguous().to(torch.float32).reshape(1), "grad_loss")
+        grads = [torch.empty_like(p) for p in ps]
+        with torch.cuda.device(gt.device):
+            for i, (p, g) in enumerate(zip(ps, grads)):
+                _call("az_seq_loss_bwd", _p(g), _p(p), _p(gt), _p(valid), *ctx.args, _p(gloss),
+                      acc.data_ptr() + 24 * i, ctx.weights[i], gt.numel(), _stream())
+        return (None,) * 6 + tuple(grads)
+
+
+def sequence_loss(flow_preds, flow_gt, valid, loss_gamma=0.9, max_flow=700, check=False, *, disparity=False):
+    """sum_i w_i * mean |flow_preds[i] - (-flow_gt)| over the pixels with valid >= 0.5 and |flow_gt| < max_flow
+    (utils/losses.py:34-69), w_i = g^(n-1-i), g = loss_gamma^(15/(n-1)).  For n = 1 the reference divides by zero;
+    here the single prediction has weight 1.  All maps [B,1,H,W]; valid fp32, uint8 or bool.
+    One autograd node for the whole list, one accumulator vector, n forward and n backward launches, no boolean
+    indexing and no host sync -- unless check=True, which reads the non-finite counter (one sync) and raises
+    AssertionError as the reference's assertions would.  disparity=True: the predictions already are
+    disparities (convex_upsample(..., negate=True)), so the target is +flow_gt."""
+    preds = list(flow_preds)
+    n = len(preds)
+    if n < 1:
+        raise AssertionError("sequence_loss needs at least one prediction")
+    gp = float(loss_gamma) ** (15.0 / (n - 1)) if n > 1 else 1.0
+    return _SeqLoss.apply(flow_gt, valid, (gp, n - 1), max_flow, 1 if disparity else -1, bool(check), *preds)

@@ -581,6 +581,44 @@ int az_disp_metrics(double *acc8, const float *disp_gt, const float *depth_gt,
                     const float *disp_pred, const float *depth_pred, const float *focal_x_baseline,
                     const unsigned char *mask, int B, long long per_batch, void *stream);
 
+/* ---- K15: RAFT-Stereo convex upsampling (az_convex_up.hip) -------------------------------------
+ * Replaces nets/raft/raft_stereo.py:74-86 `RAFTStereo.upsample_flow` (softmax over the 9 taps of a materialised
+ * [N,1,9,f,f,h,w] view, F.unfold of the flow, a materialised 9 f f-channel product, sum, permute + reshape), with the
+ * `flow_up[:, :1]` of raft_stereo.py:189 (D_out = 1: the y channel is never computed) and the `-output[-1]` of
+ * utils/losses.py:117 (sign = -1) folded in on request.
+ * flow [N,D,h,w] f32, D in {1,2}; mask [N,mask_channels,h,w], mask_channels = 9 f f, f = factor in {4,8}
+ * (cfg.MODEL.N_DOWNSAMPLE 2 / 3), channel k f f + i f + j with k = ky 3 + kx; fp32, or fp16 with mask_f16 != 0 (what the
+ * mask head emits under autocast).  The arithmetic is fp32, with one exception: the backward of an fp16 mask evaluates the
+ * softmax terms and the bracket of g_mask in fp64 and rounds once to fp16 -- fp16 subnormals resolve 6e-8 absolute, which an
+ * fp32 evaluation of a cancelling bracket misses by tens of ulp.  up and g_up are accessed as float4: 16-byte aligned, else
+ * AZ_EINVAL.  up [N,D_out,f h,f w] f32, 1 <= D_out <= D:
+ *   up[n,d,y f+i,x f+j] = sign * sum_k softmax_k(mask[n,k,i,j,y,x]) * f * flow[n,d,y+ky-1,x+kx-1]   (zero outside the map)
+ * sign = +1 or -1.  Any other factor, D or channel count: AZ_EUNSUPPORTED. */
+int az_convex_up_fwd(float *up, const float *flow, const void *mask, int mask_f16, int N, int D, int D_out, int h,
+                     int w, int factor, int mask_channels, int sign, void *stream);
+/* bytes of the backward's workspace: the per-pixel tap sums [N,D_out,9,h,w] f32 (9/(9 f f) of the mask) */
+long long az_convex_up_bwd_workspace(int N, int D_out, int h, int w);
+/* g_mask (the mask's shape and dtype, fully written) = p_k (g F_k - sum_m p_m g F_m) with the softmax recomputed from the
+ * mask; g_flow [N,D,h,w] (fully written, channels >= D_out zero), summed in a fixed order: no float atomics, bit-reproducible.
+ * g_up [N,D_out,f h,f w] f32.  Nothing needs pre-zeroing. */
+int az_convex_up_bwd(void *g_mask, float *g_flow, void *workspace, long long workspace_bytes, const float *g_up,
+                     const float *flow, const void *mask, int mask_f16, int N, int D, int D_out, int h, int w,
+                     int factor, int mask_channels, int sign, void *stream);
+
+/* ---- K16: one prediction's term of the sequence loss (az_convex_up.hip) ------------------------
+ * Replaces the loop body of utils/losses.py:34-69 `sequence_loss` (boolean-index compaction of every prediction, two
+ * .any() assertions per prediction).  pred, gt: [B,1,H,W] f32 flattened to n elements; valid: f32, or one byte per pixel
+ * with valid_u8 != 0.  A pixel counts when valid >= 0.5 and |gt| < max_flow (losses.py:45-48).  The target is
+ * tsign * gt: tsign = -1 for a flow prediction (losses.py:42), +1 when the prediction already is a disparity.
+ * acc3 (caller-zeroed fp64): [0] += sum |pred - target| over the valid pixels, [1] += their count,
+ * [2] += the number of non-finite pred values (the reference's assertions of losses.py:53-56, as a counter). */
+int az_seq_loss_fwd(double *acc3, const float *pred, const float *gt, const void *valid, int valid_u8,
+                    float max_flow, int tsign, long long n, void *stream);
+/* g_pred = weight * gloss[0] / acc3[1] * sign(pred - target) on valid pixels (sign(0) = 0), 0 elsewhere */
+int az_seq_loss_bwd(float *g_pred, const float *pred, const float *gt, const void *valid, int valid_u8,
+                    float max_flow, int tsign, const float *gloss, const double *acc3, float weight, long long n,
+                    void *stream);
+
 /* ---- K3+K4 factored: dres0[0] applied to the concat cost volume without the volume -------------
  * (nets/psmnet/psmnet_3.py:149-166).  F = the left map convolved with the NC x 5 depth-class /
  * staircase-offset variants of the depth-summed 3x3 kernels (bulk + edge maps, below); G: [B,H,W+2,NC*64] = the right map (two zero

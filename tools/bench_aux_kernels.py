@@ -1,9 +1,131 @@
 #!/usr/bin/env python3
 """Microbenchmarks of the bandwidth-class kernels at BASELINE.json's full size
 (B=4, 544x960, D=192): time per launch (HIP events on the launch stream) against the
-ALGORITHMIC bytes of SURVEY.md 8(d).  Prints a markdown table."""
+ALGORITHMIC bytes of SURVEY.md 8(d).  Prints a markdown table.
+
+    python tools/bench_aux_kernels.py raft_head [out.json]
+runs the RAFT-Stereo prediction head instead (K15 convex upsampling + K16 sequence loss, 22 iterations forward and
+backward at mask [4,144,136,240]) beside the reference's arithmetic in PyTorch eager, and prints one JSON record."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def raft_head(out_path=None):
+    import json
+    import statistics
+    import bench as _bench
+    from activezero_amd import ops
+    dev = torch.device("cuda:0")
+    B, h, w, f, iters, reps = 4, 136, 240, 4, 22, 20
+    g = torch.Generator(device=dev).manual_seed(0)
+    gt = 2.0 + 90.0 * torch.rand(B, 1, f * h, f * w, device=dev, generator=g)
+    valid = (torch.rand(B, 1, f * h, f * w, device=dev, generator=g) > 0.1).float()
+    flows = [torch.cat([-gt[:, :, ::f, ::f] / f + torch.randn(B, 1, h, w, device=dev, generator=g),
+                        torch.zeros(B, 1, h, w, device=dev)], 1).contiguous().requires_grad_() for _ in range(iters)]
+    masks = [(2.0 * torch.randn(B, 9 * f * f, h, w, device=dev, generator=g)).requires_grad_() for _ in range(iters)]
+
+    # the reference's arithmetic, restated: softmax over the 9 taps of the [N,1,9,f,f,h,w] view, 3x3 unfold of f * flow,
+    # materialised product, sum, permute; then the masked L1 means with their finiteness assertions
+    def eager_up(flow, mask):
+        n, d = flow.shape[:2]
+        p = torch.softmax(mask.view(n, 1, 9, f, f, h, w), dim=2)
+        u = torch.nn.functional.unfold(f * flow, [3, 3], padding=1).view(n, d, 9, 1, 1, h, w)
+        return torch.sum(p * u, dim=2).permute(0, 1, 4, 2, 5, 3).reshape(n, d, f * h, f * w)[:, :1]
+
+    def eager_loss(preds, gt, valid, gamma=0.9, max_flow=700):
+        t = -gt
+        ok = (valid >= 0.5) & (t.abs() < max_flow)
+        assert not torch.isinf(t[ok]).any()
+        n, loss = len(preds), 0.0
+        for i, p in enumerate(preds):
+            assert not torch.isnan(p).any() and not torch.isinf(p).any()
+            loss = loss + (gamma ** (15 / (n - 1))) ** (n - i - 1) * (p - t).abs()[ok].mean()
+        return loss
+
+    def ours():
+        loss = ops.sequence_loss([ops.convex_upsample(a, b, f, channels=1) for a, b in zip(flows, masks)], gt, valid)
+        loss.backward()
+
+    def eager():
+        eager_loss([eager_up(a, b) for a, b in zip(flows, masks)], gt, valid).backward()
+
+    def leg(fn):
+        for t in flows + masks:
+            t.grad = None
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        return {"ms_per_22_iterations": statistics.median(ms), "min_ms": min(ms), "repeats": reps,
+                "peak_MB_above_resident": (torch.cuda.max_memory_allocated() - base) / 1e6}
+
+    def kernel(fn, nbytes):
+        """fn(i) launches on the i-th of the 22 buffer sets (1.65 GB of fp32 masks: no launch finds its mask in the 256 MiB
+        cache, as in the training step); one event pair around the 22 launches"""
+        for _ in range(2):
+            for i in range(iters):
+                fn(i)
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(iters):
+                fn(i)
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / iters)
+        m = statistics.median(ms)
+        return {"ms": m, "algorithmic_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6, "launches_per_timing": iters,
+                "buffers": "rotated over %d sets" % iters}
+
+    rec = {"case": "raft_head", "mask": [B, 9 * f * f, h, w], "iterations": iters, "ours": leg(ours), "eager": leg(eager)}
+    for t in flows + masks:
+        t.grad = None
+    with torch.no_grad():
+        fls, mks = [t.detach() for t in flows], [t.detach() for t in masks]
+        mbytes, ubytes, fbytes = 4.0 * mks[0].numel(), 4.0 * B * f * h * f * w, 4.0 * fls[0].numel()
+        ups = [torch.randn(B, 1, f * h, f * w, device=dev) for _ in range(iters)]
+        gms = [torch.empty_like(m) for m in mks]
+        gf = torch.empty_like(fls[0])
+        ws = torch.empty(B * 9 * h * w, device=dev)
+        wbytes = 4.0 * ws.numel()
+        args = (0, B, 2, 1, h, w, f, 9 * f * f, 1)
+        rec["K15_fwd"] = kernel(lambda i: ops._call("az_convex_up_fwd", ups[i].data_ptr(), fls[i].data_ptr(),
+                                                    mks[i].data_ptr(), *args, ops._stream()), mbytes + fbytes + ubytes)
+        rec["K15_bwd"] = kernel(lambda i: ops._call("az_convex_up_bwd", gms[i].data_ptr(), gf.data_ptr(), ws.data_ptr(),
+                                                    4 * ws.numel(), ups[i].data_ptr(), fls[i].data_ptr(),
+                                                    mks[i].data_ptr(), *args, ops._stream()),
+                                2 * mbytes + ubytes + 2 * fbytes + 2 * wbytes)
+        mhs = [m.half() for m in mks]
+        del gms
+        gmhs = [torch.empty_like(m) for m in mhs]
+        args16 = (1,) + args[1:]
+        rec["K15_fwd_fp16_mask"] = kernel(lambda i: ops._call("az_convex_up_fwd", ups[i].data_ptr(), fls[i].data_ptr(),
+                                                              mhs[i].data_ptr(), *args16, ops._stream()),
+                                          mbytes / 2 + fbytes + ubytes)
+        rec["K15_bwd_fp16_mask"] = kernel(lambda i: ops._call("az_convex_up_bwd", gmhs[i].data_ptr(), gf.data_ptr(),
+                                                              ws.data_ptr(), 4 * ws.numel(), ups[i].data_ptr(),
+                                                              fls[i].data_ptr(), mhs[i].data_ptr(), *args16, ops._stream()),
+                                          mbytes + ubytes + 2 * fbytes + 2 * wbytes)
+    rec["copy_probe_GB/s"] = _bench.hbm_probe(dev)["GB/s"]
+    rec["speedup_vs_eager"] = rec["eager"]["ms_per_22_iterations"] / rec["ours"]["ms_per_22_iterations"]
+    rec["mask_sized_tensor_MB"] = 4.0 * B * 9 * f * f * h * w / 1e6
+    line = json.dumps(rec)
+    print(line)
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(rec, indent=1) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "raft_head":
+    raft_head(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 from activezero_amd import ops, conv3d
 from activezero_amd.utils import reprojection as rp, warp_ops
 from activezero_amd.nets.raft.corr import CorrBlock1D

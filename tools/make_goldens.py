@@ -10,9 +10,10 @@ Harness-side shims (none of them edits the reference):
   * empty stand-in modules for `cupy` / `pynvrtc` so that utils/reprojection.py
     (which imports utils/warp_ops.py at module level) can be imported; the
     NVRTC scatter warp itself is NOT run (it cannot be, see DESIGN.md);
-  * (G12 / G13 only) inert stand-ins for `opt_einsum` and `configs.config`: nets/raft/update.py and
-    utils/losses.py import them at module level, but neither `ConvGRU` (update.py:19-41) nor `psmnet_disp`
-    (losses.py:7-15) reads anything from them.
+  * (G12 / G13 / G14 only) inert stand-ins for `opt_einsum` and `configs.config`: nets/raft/update.py,
+    nets/raft/raft_stereo.py and utils/losses.py import them at module level, but neither `ConvGRU`
+    (update.py:19-41), `psmnet_disp` (losses.py:7-15) nor `sequence_loss` (losses.py:34-69) reads anything from
+    them; `RAFTStereo.upsample_flow` reads cfg.MODEL.N_DOWNSAMPLE, which G14 sets on the stand-in.
 """
 import os
 import sys
@@ -567,10 +568,72 @@ def g13_full_train_d192():
     save("g13_psmnet3_train_d192", seeds=[1103, 1104, 1301], maxdisp=maxdisp, pred_stride=st, **out)
 
 
+# ---------------------------------------------------------------- G14 RAFT-Stereo prediction head
+def g14_raft_head():
+    """nets/raft/raft_stereo.py:74-86 `RAFTStereo.upsample_flow` (called unbound: it reads nothing from self) and
+    utils/losses.py:34-69 `sequence_loss`, both imported from the reference, in fp32 and fp64; the upsampling also with
+    the mask rounded to fp16 and evaluated as under cfg.MODEL.MIXED_PRECISION (the mask head's output is fp16 there:
+    softmax in fp16, product with the fp32 flow in fp32) beside fp64 of the same fp16-valued inputs.  Inputs are
+    regenerated from the seeds by the tests; the large outputs are stored on lattices (`*_lat` = the strides)."""
+    from tests._raft_head_ref import make_mask_logits
+    rs = _import_with_inert_stubs("nets.raft.raft_stereo")
+    losses = _import_with_inert_stubs("utils.losses")
+    cfg = sys.modules["configs.config"].cfg
+    out = {}
+    # tag, factor, flow shape, zero the y channel, seed
+    cases = [("a", 4, (2, 2, 9, 13), False, 1401), ("b", 8, (1, 2, 5, 7), True, 1411)]
+    up_lat, gm_lat = (3, 3), (3, 4)  # 3 is coprime to both factors: every sub-pixel (i, j) is sampled
+    for tag, f, shape, zero_y, sd in cases:
+        cfg.MODEL = types.SimpleNamespace(N_DOWNSAMPLE={4: 2, 8: 3}[f])
+        n, d, h, w = shape
+        flow = seeded(shape, sd, -3.0, 3.0)
+        if zero_y:
+            flow[:, 1] = 0.0
+        mask = make_mask_logits((n, 9 * f * f, h, w), sd + 1)
+        cot = seeded((n, d, f * h, f * w), sd + 2)
+        out[f"{tag}_meta"] = np.array([f, n, d, h, w, sd, int(zero_y)])
+
+        def run(fl, mk, key):
+            fl, mk = fl.clone().requires_grad_(True), mk.clone().requires_grad_(True)
+            up = rs.RAFTStereo.upsample_flow(None, fl, mk)
+            gf, gm = torch.autograd.grad(up, (fl, mk), cot.to(up.dtype))
+            out[f"{tag}_up{key}"] = up[..., ::up_lat[0], ::up_lat[1]]
+            out[f"{tag}_gflow{key}"] = gf
+            out[f"{tag}_gmask{key}"] = gm[..., ::gm_lat[0], ::gm_lat[1]]
+            return up, gf, gm
+
+        r32 = run(flow, mask, "32")
+        r64 = run(flow.double(), mask.double(), "64")
+        m16 = mask.half()
+        ramp = run(flow, m16, "_amp")  # fp16 softmax, fp32 product; g_mask comes back in fp16
+        r64h = run(flow.double(), m16.double(), "64_h")
+        for name, a, b in (("fp32", r32, r64), ("amp", ramp, r64h)):
+            print(f"  g14 {tag} {name}: max |ref - ref64| up {(a[0].double() - b[0]).abs().max():.3e} "
+                  f"gflow {(a[1].double() - b[1]).abs().max():.3e} gmask {(a[2].double() - b[2]).abs().max():.3e}")
+    # sequence loss: [2,1,36,52], a zero region in valid, some |gt| >= max_flow
+    shape, sd = (2, 1, 36, 52), 1421
+    gt = seeded(shape, sd, -40.0, 820.0)
+    valid = (seeded(shape, sd + 1, 0.0, 1.0) > 0.1).float()
+    valid[:, :, 5:17, 20:41] = 0.0
+    st = 2
+    for n_pred in (4, 22):
+        preds = [-gt + seeded(shape, sd + 10 + i, -3.0, 3.0) * (1.0 + 0.2 * (n_pred - i)) for i in range(n_pred)]
+        for tag, dt in (("32", torch.float32), ("64", torch.float64)):
+            ps = [p.to(dt).requires_grad_(True) for p in preds]
+            loss = losses.sequence_loss(ps, gt.to(dt), valid.to(dt), loss_gamma=0.9, max_flow=700)
+            grads = torch.autograd.grad(loss, ps)
+            out[f"s{n_pred}_loss{tag}"] = loss
+            out[f"s{n_pred}_grads{tag}"] = torch.stack(grads)[..., ::st, ::st]
+        print(f"  g14 seq n={n_pred}: loss32 {out[f's{n_pred}_loss32'].item():.7f} loss64 {out[f's{n_pred}_loss64'].item():.7f}")
+    save("g14_raft_head", seeds=[1401, 1411, 1421], up_lat=up_lat, gmask_lat=gm_lat, seq_lat=st, max_flow=700.0,
+         loss_gamma=0.9, **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     only = set(sys.argv[1:])
     for fn in (g1_cost_volume, g2_softargmin, g3_blocks, g4_full, g6_apply_disparity, g7_patch,
-               g8_lcn, g9_corr, g10_metrics, g11_full_d192, g12_convgru, g13_full_train_d192):
+               g8_lcn, g9_corr, g10_metrics, g11_full_d192, g12_convgru, g13_full_train_d192,
+               g14_raft_head):
         if not only or fn.__name__.split("_")[0] in only:
             fn()
