@@ -6,6 +6,8 @@ import ctypes
 import os
 import re
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AZ_LIB_PATH") or os.path.join(HERE, "lib", "libazhip.so")  # AZ_LIB_PATH: kernel A/B experiments
 HEADER = os.path.join(HERE, "..", "include", "azhip.h")
@@ -13,146 +15,108 @@ HEADER = os.path.join(HERE, "..", "include", "azhip.h")
 _lib = None
 
 _C = ctypes
-_PTR, _INT, _SIZE, _LL = _C.c_void_p, _C.c_int, _C.c_size_t, _C.c_longlong
+_PTR, _INT = _C.c_void_p, _C.c_int
+_SCALARS = {"int": _INT, "long long": _C.c_longlong, "float": _C.c_float, "double": _C.c_double, "size_t": _C.c_size_t}
+_FIELDS = {"int": "i4", "long long": "i8"}  # members of the descriptor structs; a pointer is "u8"
+_DIRECTIVES = re.compile(r"#\s*(ifndef AZHIP_H|ifdef __cplusplus|endif|include\s*<\w+\.h>|define AZHIP_H)\s*")
+_CALL = re.compile(r"\baz_[a-z0-9_]+\s*\(")
+_PROTO = re.compile(r"([\w\s*]*?)\b(az_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;")
 
-# name -> argtypes (return type is int unless listed in _RESTYPE)
-_SIGS = {
-    "az_abi_version": [],
-    "az_hbm_copy_probe": [_PTR, _PTR, _LL, _PTR],
-    "az_option": [_C.c_char_p],
-    "az_strerror": [_INT],
-    "az_warp_scatter": [_PTR, _PTR, _PTR, _INT, _INT, _INT, _INT, _INT, _PTR],
-    "az_cost_volume_fwd": [_PTR] * 3 + [_INT] * 5 + [_PTR],
-    "az_cost_volume_bwd": [_PTR] * 3 + [_INT] * 5 + [_PTR],
-    "az_cost_volume_fwd_ndhwc": [_PTR] * 3 + [_INT] * 5 + [_PTR],
-    "az_cost_volume_bwd_ndhwc": [_PTR] * 3 + [_INT] * 5 + [_PTR],
-    "az_softargmin_fwd": [_PTR] * 3 + [_INT] * 4 + [_PTR],
-    "az_softargmin_bwd": [_PTR] * 5 + [_INT] * 4 + [_PTR],
-    "az_warp_gather_fwd": [_PTR] * 3 + [_INT] * 4 + [_PTR],
-    "az_warp_gather_bwd": [_PTR] * 5 + [_INT] * 4 + [_PTR],
-    "az_patch_reproj_fwd": [_PTR] * 5 + [_INT] * 5 + [_C.c_float, _PTR],
-    "az_patch_reproj_bwd": [_PTR] * 7 + [_INT] * 5 + [_C.c_float, _PTR],
-    "az_patch_reproj_vis": [_PTR] * 3 + [_INT] * 5 + [_C.c_float, _PTR],
-    "az_lcn": [_PTR] * 3 + [_INT] * 4 + [_C.c_float, _C.c_longlong, _PTR],
-    "az_sum4": [_PTR] * 5 + [_LL, _PTR],
-    "az_spp_upsample_fwd": [_PTR, _PTR] + [_INT] * 7 + [_PTR],
-    "az_spp_upsample_bwd_workspace": [_INT] * 4,
-    "az_spp_upsample_bwd": [_PTR, _PTR, _LL, _PTR] + [_INT] * 7 + [_PTR],
-    "az_costconv_edge_width": [_INT, _INT],
-    "az_costconv_num_classes": [_INT],
-    "az_costconv_merge_fwd": [_PTR] * 5 + [_INT, _PTR],
-    "az_costconv_merge_bwd": [_PTR] * 5 + [_INT, _PTR],
-    "az_costconv_assemble_fwd": [_PTR] * 4 + [_INT] * 4 + [_PTR],
-    "az_costconv_assemble_bwd": [_PTR] * 4 + [_INT] * 4 + [_PTR],
-    "az_bn3d_stats_tiles": [_LL, _INT],
-    "az_bn3d_stats": [_PTR] * 3 + [_LL, _INT, _PTR],
-    "az_bn2d_workspace": [_INT, _LL, _INT],
-    "az_bn2d_fwd": [_PTR] * 12 + [_LL, _INT, _INT, _LL, _INT, _C.c_float, _C.c_float, _PTR, _PTR, _PTR, _LL, _PTR, _PTR],
-    "az_conv2d_stats_tiles": [_INT] * 4,
-    "az_conv2d_fwd_stats": [_PTR] * 5 + [_INT] * 11 + [_PTR],
-    "az_conv2d_roll_packed_floats": [_INT] * 2,
-    "az_conv2d_roll_pack": [_PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _PTR],
-    "az_conv2d_roll_fwd": [_PTR] * 6 + [_INT] * 6 + [_PTR],
-    "az_conv2d_roll_stats_rows": [_INT] * 6,
-    "az_conv2d_roll_fwd_stats": [_PTR] * 5 + [_INT] * 6 + [_PTR],
-    "az_bn2d_bwd": [_PTR] * 5 + [_LL] + [_PTR] * 8 + [_INT, _INT, _LL, _INT, _PTR, _PTR],
-    "az_conv2d_pack_weights_f16": [_PTR, _PTR, _PTR] + [_INT] * 4 + [_LL, _LL] + [_INT] * 3 + [_PTR],
-    "az_conv2d_fwd_f16": [_PTR] * 8 + [_INT] * 12 + [_PTR],
-    "az_conv2d_fwd_stats_f16": [_PTR] * 7 + [_INT] * 11 + [_PTR],
-    "az_conv2d_pack_weights_bf16_flipped": [_PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _INT, _PTR],
-    "az_conv2d_wgrad_bf16": [_PTR, _PTR, _LL, _PTR, _PTR] + [_INT] * 9 + [_PTR],
-    "az_conv2d_wgrad_f16": [_PTR, _PTR, _LL] + [_PTR] * 4 + [_INT] * 12 + [_PTR],
-    "az_conv2d_roll_pack_f16": [_PTR, _PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _PTR],
-    "az_conv2d_roll_fwd_f16": [_PTR] * 8 + [_INT] * 6 + [_PTR],
-    "az_conv2d_roll_fwd_stats_f16": [_PTR] * 7 + [_INT] * 6 + [_PTR],
-    "az_disp_loss_fwd": [_PTR] * 6 + [_C.c_float, _C.c_float, _C.c_longlong, _PTR],
-    "az_disp_loss_bwd": [_PTR] * 8 + [_C.c_float, _C.c_float, _PTR, _PTR] + [_C.c_float] * 3 + [_C.c_longlong, _PTR],
-    "az_disp_metrics": [_PTR] * 7 + [_INT, _C.c_longlong, _PTR],
-    "az_convex_up_fwd": [_PTR] * 3 + [_INT] * 9 + [_PTR],
-    "az_convex_up_bwd_workspace": [_INT] * 4,
-    "az_convex_up_bwd": [_PTR] * 3 + [_LL] + [_PTR] * 3 + [_INT] * 9 + [_PTR],
-    "az_seq_loss_fwd": [_PTR] * 4 + [_INT, _C.c_float, _INT, _LL, _PTR],
-    "az_seq_loss_bwd": [_PTR] * 4 + [_INT, _C.c_float, _INT, _PTR, _PTR, _C.c_float, _LL, _PTR],
-    "az_conv3d_packed_floats": [_INT, _INT, _INT],
-    "az_conv3d_pack_weights": [_PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _INT, _PTR],
-    "az_conv3d_num_tiles": [_INT] * 5,
-    "az_conv3d_stats_tiles": [_INT] * 8,
-    "az_conv3d_fwd": [_PTR] * 7 + [_INT] * 10 + [_PTR],
-    "az_conv3d_fwd_stats": [_PTR] * 6 + [_INT] * 9 + [_PTR],
-    "az_conv3d_wgrad_workspace": [_INT, _INT],
-    "az_conv3d_wgrad": [_PTR, _PTR, _LL, _PTR, _PTR] + [_INT] * 11 + [_PTR],
-    "az_absmax": [_PTR, _PTR, _LL, _PTR],
-    "az_pack_f16_multi": [_PTR, _PTR, _PTR, _INT, _INT, _PTR],
-    "az_wgrad_unpack_multi": [_PTR, _PTR, _PTR, _INT, _INT, _PTR],
-    "az_conv3d_packed_floats_f16": [_INT, _INT],
-    "az_conv3d_f16_layout": [_INT, _INT, _INT],
-    "az_conv3d_pack_weights_f16": [_PTR, _PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _INT, _PTR],
-    "az_conv3d_fwd_f16": [_PTR] * 5 + [_INT] + [_PTR] * 3 + [_INT] * 8 + [_PTR],
-    "az_conv3d_fwd_f16_split_ok": [_INT] * 7,
-    "az_conv3d_wgrad_f16_split_ok": [_INT] * 10,
-    "az_conv3d_stats_tiles_f16": [_INT] * 7,
-    "az_conv3d_fwd_stats_f16": [_PTR] * 7 + [_INT] * 7 + [_PTR],
-    "az_conv3d_wgrad_f16": [_PTR, _PTR, _LL] + [_PTR] * 4 + [_INT] * 11 + [_PTR],
-    "az_conv3d_c1_fwd": [_PTR] * 6 + [_INT] * 4 + [_PTR],
-    "az_conv3d_c1_dgrad": [_PTR] * 3 + [_INT] * 4 + [_PTR],
-    "az_conv3d_c1_wgrad": [_PTR] * 5 + [_INT] * 4 + [_PTR],
-    "az_bn3d_finalize": [_PTR] * 10 + [_LL, _INT, _C.c_float, _C.c_float, _PTR, _PTR, _LL, _PTR],
-    "az_bn3d_finalize_scratch": [_INT],
-    "az_bn3d_eval_affine": [_PTR] * 6 + [_C.c_float, _INT, _PTR],
-    "az_bn3d_apply": [_PTR] * 5 + [_INT, _LL, _INT, _PTR, _PTR],
-    "az_bn3d_bwd_workspace": [_LL, _INT],
-    "az_bn3d_bwd": [_PTR] * 6 + [_LL] + [_PTR] * 8 + [_INT, _LL, _INT, _PTR, _INT, _PTR],
-    "az_add_relu": [_PTR] * 3 + [_INT, _LL, _PTR, _PTR],
-    "az_conv2d_packed_floats": [_INT] * 4,
-    "az_conv2d_pack_weights": [_PTR, _PTR] + [_INT] * 4 + [_LL, _LL] + [_INT] * 3 + [_PTR],
-    "az_conv2d_fwd": [_PTR] * 6 + [_INT] * 12 + [_PTR],
-    "az_rows_concat": [_PTR, _LL, _LL, _INT, _PTR, _PTR, _PTR, _PTR],
-    "az_rows_slice_to_image": [_PTR, _PTR, _LL, _LL, _INT, _INT, _INT, _PTR],
-    "az_gru_rh": [_PTR] * 3 + [_LL, _INT, _INT, _PTR],
-    "az_gru_out": [_PTR] * 4 + [_LL, _INT, _INT, _PTR],
-    "az_gru_bwd1": [_PTR] * 7 + [_LL, _INT, _INT, _PTR, _PTR, _PTR],
-    "az_gru_bwd2": [_PTR] * 5 + [_LL, _INT, _INT, _PTR, _PTR],
-    "az_conv2d_pack_weights_h1": [_PTR, _PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _PTR],
-    "az_conv2d_h1_fwd": [_PTR] * 9 + [_INT] * 11 + [_PTR],
-    "az_conv2d_wgrad_h1": [_PTR, _PTR, _LL] + [_PTR] * 4 + [_INT] * 9 + [_PTR],
-    "az_gru_bwd3": [_PTR] * 5 + [_LL, _INT, _INT, _PTR],
-    "az_conv2d_pack_weights_bf16": [_PTR, _PTR, _INT, _INT, _LL, _LL, _INT, _INT, _PTR],
-    "az_conv2d_bf16_fwd": [_PTR] * 7 + [_INT] * 11 + [_PTR],
-    "az_conv2d_wgrad_workspace": [_INT] * 4,
-    "az_conv2d_wgrad": [_PTR, _PTR, _LL, _PTR, _PTR] + [_INT] * 12 + [_PTR],
-    "az_im2col_s2k3": [_PTR, _PTR] + [_INT] * 5 + [_PTR],
-    "az_col2im_s2k3": [_PTR, _PTR] + [_INT] * 5 + [_PTR],
-    "az_ir_pattern_workspace": [_INT] * 4,
-    "az_ir_pattern": [_PTR, _PTR, _LL, _PTR, _PTR] + [_INT] * 4 + [_C.c_float, _PTR],
-    "az_corr1d_volume": [_PTR] * 3 + [_INT] * 5 + [_PTR],
-    "az_corr1d_volume_bwd": [_PTR] * 5 + [_INT] * 5 + [_PTR],
-    "az_corr1d_pool": [_PTR, _PTR, _LL, _INT, _PTR],
-    "az_corr1d_pool_bwd": [_PTR, _PTR, _LL, _INT, _PTR],
-    "az_corr1d_lookup_fwd": [_PTR] * 3 + [_INT] * 8 + [_PTR],
-    "az_corr1d_lookup_bwd": [_PTR] * 3 + [_INT] * 8 + [_PTR],
-    "az_corr1d_lookup_bwd_acc": [_PTR] * 3 + [_INT] * 8 + [_PTR],
-}
-_RESTYPE = {"az_strerror": _C.c_char_p, "az_conv3d_num_tiles": _LL, "az_conv3d_stats_tiles": _LL, "az_conv2d_roll_packed_floats": _LL, "az_conv2d_roll_stats_rows": _LL, "az_conv3d_packed_floats": _LL, "az_conv3d_packed_floats_f16": _LL, "az_conv3d_stats_tiles_f16": _LL,
-            "az_conv3d_wgrad_workspace": _LL, "az_bn3d_bwd_workspace": _LL, "az_spp_upsample_bwd_workspace": _LL,
-            "az_bn3d_stats_tiles": _LL, "az_bn2d_workspace": _LL,
-            "az_conv2d_packed_floats": _LL, "az_conv2d_wgrad_workspace": _LL, "az_ir_pattern_workspace": _LL,
-            "az_bn3d_finalize_scratch": _LL, "az_conv2d_stats_tiles": _LL,
-            "az_convex_up_bwd_workspace": _LL}
+
+def _ctype(decl, where):
+    """ctypes type of `type [name]`: any pointer is a void pointer, except `const char *`"""
+    decl = " ".join(decl.split())
+    if "*" in decl:
+        return _C.c_char_p if decl.split("*")[0].strip() == "const char" else _PTR
+    m = re.fullmatch(r"(?:const )?(int|long long|float|double|size_t)(?: \w+)?", decl)
+    if m is None:
+        raise RuntimeError(f"azhip.h: {where}: unknown type in '{decl}'")
+    return _SCALARS[m.group(1)]
+
+
+def _struct_dtype(name, body):
+    """numpy structured dtype of a descriptor struct, laid out as the C compiler lays it out"""
+    names, formats = [], []
+    for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+        ptr = re.fullmatch(r"(?:const )?\w+ \*(\w+)", decl)
+        val = re.fullmatch(r"(int|long long) (\w+(?:, \w+)*)", decl)
+        if ptr is None and val is None:
+            raise RuntimeError(f"azhip.h: struct {name}: unknown member '{decl}'")
+        members = [ptr.group(1)] if ptr else val.group(2).split(", ")
+        names += members
+        formats += ["u8" if ptr else _FIELDS[val.group(1)]] * len(members)
+    return np.dtype({"names": names, "formats": formats}, align=True)
+
+
+def _constant(name, expr, known):
+    """value of an integer #define: a literal, a parenthesised negative, or a product of literals and earlier constants"""
+    expr = expr.strip()
+    if expr.startswith("(") and expr.endswith(")"):
+        expr = expr[1:-1]
+    value = 1
+    for term in (t.strip() for t in expr.split("*")):
+        if re.fullmatch(r"-?\d+", term):
+            value *= int(term)
+        elif term in known:
+            value *= known[term]
+        else:
+            raise RuntimeError(f"azhip.h: #define {name}: '{term}' is neither an integer nor an earlier AZ_* constant")
+    return value
+
+
+def parse_header(text):
+    """(argtypes, non-int restypes, constants, struct dtypes) of the header `text`; RuntimeError for anything in it that
+    is not a comment, a known directive, an integer `#define AZ_*`, a struct of pointers / int / long long, or a prototype
+    `type az_name(args);` -- nothing is skipped"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    const, lines = {}, []
+    for line in text.split("\n"):
+        m = re.fullmatch(r"\s*#\s*define\s+(AZ_\w+)\s+(.*)", line)
+        if m is not None:
+            const[m.group(1)] = _constant(m.group(1), m.group(2), const)
+        elif not line.lstrip().startswith("#"):
+            lines.append(line)
+        elif _DIRECTIVES.fullmatch(line.strip()) is None:  # (a conditional could hide a declaration from the compiler)
+            raise RuntimeError(f"azhip.h: directive '{line.strip()}' is not understood")
+    text = "\n".join(lines)
+    structs = {}
+    for m in _STRUCT.finditer(text):
+        if m.group(1) != m.group(3):
+            raise RuntimeError(f"azhip.h: struct {m.group(1)} is typedef'd as {m.group(3)}")
+        structs[m.group(1)] = _struct_dtype(m.group(1), m.group(2))
+    text = _STRUCT.sub(" ", text)
+    sigs, restype = {}, {}
+    for ret, name, args in _PROTO.findall(text):
+        if name in sigs:
+            raise RuntimeError(f"azhip.h: {name} is declared twice")
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        sigs[name] = [_ctype(a, name) for a in args]
+        res = _ctype(ret, f"return type of {name}")
+        if res is not _INT:
+            restype[name] = res
+    calls = len(_CALL.findall(text))
+    rest = _PROTO.sub(" ", text).replace('extern "C" {', " ").replace("}", " ").strip()
+    if calls != len(sigs) or rest:
+        raise RuntimeError(f"azhip.h: {calls} az_*( occurrences but {len(sigs)} prototypes parsed; not understood: '{rest[:200]}'")
+    return sigs, restype, const, structs
+
+
+# include/azhip.h is the only statement of the ABI: argtypes per function (return type is int unless listed in
+# _RESTYPE), the integer AZ_* constants, and the descriptor structs as numpy dtypes, all read from it once, here
+with open(HEADER) as _f:
+    _SIGS, _RESTYPE, CONST, _STRUCTS = parse_header(_f.read())
+PACK_DESC, UNPACK_DESC = _STRUCTS["AzPackDesc"], _STRUCTS["AzUnpackDesc"]
 
 
 def declared_symbols():
     """Every function name include/azhip.h declares."""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(az_[a-z0-9_]+)\s*\(", text)))
+    return sorted(_SIGS)
 
 
 def expected_abi_version():
-    """AZ_ABI_VERSION of include/azhip.h: the signatures _SIGS was written against"""
-    m = re.search(r"#define\s+AZ_ABI_VERSION\s+(\d+)", open(HEADER).read())
-    if m is None:
-        raise RuntimeError(f"{HEADER} defines no AZ_ABI_VERSION")
-    return int(m.group(1))
+    """AZ_ABI_VERSION of include/azhip.h: the signatures _SIGS holds"""
+    return CONST["AZ_ABI_VERSION"]
 
 
 def lib():

@@ -14,9 +14,11 @@ import threading
 import torch
 
 from . import profiler
+from ._lib import CONST
 from .ops import _call, _p, _stream
 
-AMAX_SLOTS = 1024  # include/azhip.h AZ_AMAX_FLOATS: floats of an "amax array" (16 slots, 256 bytes apart)
+AMAX_SLOTS = CONST["AZ_AMAX_FLOATS"]  # floats of an "amax array" (include/azhip.h: 16 slots, 256 bytes apart)
+_STRIDE = CONST["AZ_AMAX_STRIDE"]    # floats from one slot to the next
 
 
 class _ZeroPool:
@@ -62,7 +64,7 @@ def check_amax(t, am):
     """raise if the amax array `am` is below the largest finite magnitude of t (a stale attribute)"""
     fresh = t.new_empty(AMAX_SLOTS)
     _call("az_absmax", _p(fresh), _p(t), t.numel(), _stream())
-    have, true = float(am[::64].max()), float(fresh[::64].max())  # (the slots: every 64th float of an amax array)
+    have, true = float(am[::_STRIDE].max()), float(fresh[::_STRIDE].max())  # (the slots of an amax array)
     if not have >= true:
         raise RuntimeError(f"stale amax: {have:.6g} attached to a tensor whose largest finite magnitude is {true:.6g} "
                            "(written through a raw pointer or .data without packing.touched / a fresh amax.absmax?)")

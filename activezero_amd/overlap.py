@@ -50,9 +50,13 @@ construction above does not apply (no grad mode, a frozen convolution weight, CP
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import profiler
+from ._lib import UNPACK_DESC
+from .ops import _call, _p
+from .packing import launch_tables
 
 _STREAMS = {}
 _STREAMS_LOCK = threading.Lock()
@@ -86,6 +90,11 @@ def side_stream(device):
         if s is None:
             s = _STREAMS[idx] = torch.cuda.Stream(device=idx, priority=_SIDE_PRIORITY)
     return s
+
+
+def unpack_tables(rows):
+    """launch_tables of az_wgrad_unpack_multi: one element per real weight"""
+    return launch_tables(UNPACK_DESC, rows, lambda r: r["cm_real"] * r["cn_real"] * r["taps"])
 
 
 _ARENA_HINT = {}   # device index -> floats of weight-gradient workspace the last pass used
@@ -153,21 +162,12 @@ class Sink:
         self.pending.append((grad_w, ws, cm, cn, cm_real, cn_real, taps))
 
     def _flush_pending(self):
-        import numpy as np
-        from .ops import _call, _p
         pend, self.pending = self.pending, []
         nd = len(pend)
-        raw = np.zeros(nd * 40, dtype=np.uint8)  # sizeof(AzUnpackDesc): 2 pointers, 6 ints
-        q, ints = raw.view(np.int64).reshape(nd, 5), raw.view(np.int32).reshape(nd, 10)
-        block_desc, first, nblocks = [], [], 0
-        for i, (gw, ws, cm, cn, cmr, cnr, taps) in enumerate(pend):
-            q[i, 0], q[i, 1] = gw.data_ptr(), ws.data_ptr()
-            ints[i, 4:9] = (cm, cn, cmr, cnr, taps)
-            nb = (cmr * cnr * taps + 255) // 256
-            first.append(nblocks)
-            block_desc.append(np.full(nb, i, dtype=np.int32))
-            nblocks += nb
-        tables = np.concatenate([raw.view(np.int32), np.concatenate(block_desc), np.asarray(first, dtype=np.int32)])
+        descs, block_desc, first, nblocks = unpack_tables([
+            dict(dst=gw.data_ptr(), ws=ws.data_ptr(), cm=cm, cn=cn, cm_real=cmr, cn_real=cnr, taps=taps)
+            for gw, ws, cm, cn, cmr, cnr, taps in pend])
+        tables = np.concatenate([descs.view(np.int32), block_desc, first])
         dev = self.stream.device
         # a FRESH pinned tensor per join, from torch's caching host allocator: the asynchronous copy below executes when the side
         # stream reaches it -- tens of milliseconds after this line, and the host may be several steps ahead of the GPU by then
@@ -177,7 +177,8 @@ class Sink:
         stage = torch.from_numpy(tables).pin_memory()
         with torch.cuda.stream(self.stream):
             t = stage.to(dev, non_blocking=True)
-            o1, o2 = nd * 10, nd * 10 + nblocks
+            o1 = nd * (UNPACK_DESC.itemsize // 4)  # (the tables are one int32 tensor)
+            o2 = o1 + nblocks
             with torch.cuda.device(dev):
                 _call("az_wgrad_unpack_multi", _p(t), _p(t[o1:o2]), _p(t[o2:]), nd, nblocks, self.stream.cuda_stream)
         self.keep.append(t)

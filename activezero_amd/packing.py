@@ -9,9 +9,11 @@ The kernels read weights from packed images, not from PyTorch's layouts.  This m
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import amax
+from ._lib import CONST, PACK_DESC
 from .amax import AMAX_SLOTS
 from .ops import _call, _p, _stream
 
@@ -76,8 +78,27 @@ def touched(*tensors):
 #   * only tensors registered through prepack() -- live nn.Parameters, held by weak reference -- have entries: derived
 #     weights (the merged kernels of K3', DataParallel replicas) change address every step and keep the per-call route;
 #   * an entry is valid for one (address, version counter): optimizer steps and load_state_dict write in place and bump it.
-PACK_2D_SAME, PACK_2D_ROLL, PACK_3D_GATHER, PACK_3D_ROLL, PACK_3D_ROLL2 = 0, 1, 2, 3, 4
+PACK_2D_SAME, PACK_2D_ROLL, PACK_3D_GATHER, PACK_3D_ROLL, PACK_3D_ROLL2 = (
+    CONST["AZ_PACK_" + k] for k in ("2D_SAME", "2D_ROLL", "3D_GATHER", "3D_ROLL", "3D_ROLL2"))
 _PLAN_ON = os.environ.get("AZ_PACK_PLAN", "1") != "0"  # (read once) 0: every image packed by its own launch, as in round 4
+
+
+def launch_tables(dtype, rows, work):
+    """The tables of az_pack_f16_multi / az_wgrad_unpack_multi (include/azhip.h) as numpy arrays: descs, one `dtype` struct
+    per row (a dict of the struct's fields; pad_ stays zero); block_desc, the descriptor of every workgroup (descriptor i has
+    work(rows[i]) elements, 256 per workgroup, its workgroups consecutive); first_block, the first workgroup of every
+    descriptor; and the number of workgroups"""
+    descs = np.zeros(len(rows), dtype=dtype)
+    for name in dtype.names:
+        if name != "pad_":
+            descs[name] = [row[name] for row in rows]
+    nb = np.array([(work(row) + 255) // 256 for row in rows], dtype=np.int64)
+    return descs, np.repeat(np.arange(len(rows), dtype=np.int32), nb), (np.cumsum(nb) - nb).astype(np.int32), int(nb.sum())
+
+
+def pack_tables(rows):
+    """launch_tables of az_pack_f16_multi: two fp16 parts per weight"""
+    return launch_tables(PACK_DESC, rows, lambda r: 2 * r["taps"] * r["cin"] * r["cout"])
 
 
 class _PackEntry:
@@ -87,7 +108,6 @@ class _PackEntry:
 
 class PackPlan:
     """the images of one device"""
-    DESC_BYTES = 72  # sizeof(AzPackDesc): 3 pointers, 2 long long, 8 ints
 
     def __init__(self, device):
         self.device = device
@@ -149,25 +169,13 @@ class PackPlan:
             return e, e.version == weight._version
 
     def _build_table(self, todo):
-        import numpy as np
-        nd = len(todo)
-        raw = np.zeros(nd * self.DESC_BYTES, dtype=np.uint8)
-        q = raw.view(np.int64).reshape(nd, self.DESC_BYTES // 8)
-        ints = raw.view(np.int32).reshape(nd, self.DESC_BYTES // 4)
-        block_desc, first = [], []
-        nblocks = 0
-        for i, e in enumerate(todo):
-            w = e.wref()
-            q[i, 0], q[i, 1], q[i, 2] = e.packed.data_ptr(), w.data_ptr(), e.amax.data_ptr()
-            q[i, 3], q[i, 4] = e.s_co, e.s_ci
-            ints[i, 10:17] = (e.kind, e.cin, e.cout, e.ci_real, e.co_real, e.taps, int(e.flip))
-            nb = (2 * e.taps * e.cin * e.cout + 255) // 256
-            first.append(nblocks)
-            block_desc.append(np.full(nb, i, dtype=np.int32))
-            nblocks += nb
+        descs, block_desc, first, nblocks = pack_tables([
+            dict(dst=e.packed.data_ptr(), src=e.wref().data_ptr(), amax=e.amax.data_ptr(), s_co=e.s_co, s_ci=e.s_ci,
+                 kind=e.kind, cin=e.cin, cout=e.cout, ci_real=e.ci_real, co_real=e.co_real, taps=e.taps, flip=e.flip)
+            for e in todo])
         dev = self.device
-        self.table = (torch.from_numpy(raw).to(dev), torch.from_numpy(np.concatenate(block_desc)).to(dev),
-                      torch.tensor(first, dtype=torch.int32, device=dev), nd, nblocks, list(todo))
+        self.table = (torch.from_numpy(descs.view(np.uint8)).to(dev), torch.from_numpy(block_desc).to(dev),
+                      torch.from_numpy(first).to(dev), len(todo), nblocks, list(todo))
 
     def prepack(self, weights):
         """register `weights` (nn.Parameters) and bring every recorded image of THEIRS up to their current version in one

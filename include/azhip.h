@@ -221,7 +221,7 @@ int az_absmax(float *amax, const float *x, long long n, void *stream);
  * rest as in those calls (taps = kh * kw or 27; ci_real / co_real < cin / cout: zero-padded channels, 2-D "same" layout
  * only).  descs: nd descriptors in DEVICE memory; block_desc: for each of the nblocks workgroups (256 elements each) the
  * descriptor it works on, blocks of one descriptor consecutive; first_block: per descriptor its first workgroup --
- * both built by the caller (activezero_amd/conv3d.py: PackPlan) once per set of weights. */
+ * both built by the caller (activezero_amd/packing.py: PackPlan) once per set of weights. */
 #define AZ_PACK_2D_SAME 0
 #define AZ_PACK_2D_ROLL 1
 #define AZ_PACK_3D_GATHER 2
