@@ -432,8 +432,6 @@ def _presplit_ok(x, raw, mode, cin, cout, need_gx, need_gw):
     same questions as _input_grad (_f16_launch_ok of the same launch) and _weight_grad ask; the library answers for
     its own kernels (az_conv3d_*_split_ok)."""
     lib = _lib.lib()
-    if lib.az_option(b"AZ_BN_BWD_FUSED") == 0:  # (the three-launch BatchNorm backward of that A/B switch writes floats only)
-        return False
     b, d, h, w, _ = raw.shape
     if need_gx:
         op, ci, co = _dgrad_launch(mode, cin, cout)[:3]

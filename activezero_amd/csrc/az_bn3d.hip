@@ -10,14 +10,12 @@
 // Eval forward: az_bn3d_eval_affine folds running stats into (scale, shift), which
 //   the conv epilogue applies directly (no extra pass).
 // Train backward (dy -> dx_raw, dgamma, dbeta, dresidual):
-//   az_bn3d_bwd_reduce: per-block partials of sum(dz), sum(dz*xhat), dz = dy*[y>0]
-//   az_bn3d_bwd_finalize: fp64 merge -> dgamma, dbeta, and the two per-channel
-//      coefficients of the apply pass
-//   az_bn3d_bwd_apply: dx = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)); optional dz out.
+//   bn_bwd_reduce_kernel: per-block partials of sum(dz), sum(dz*xhat), dz = dy*[y>0]
+//   bn_bwd_apply_kernel: in its prologue the fp64 merge -> dgamma, dbeta, and the two per-channel
+//      coefficients; then dx = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)); optional dz out.
 #include <stdlib.h>
 
 #include "az_roll_common.h"
-#include "az_options.h"
 
 // Block-wide fp64 sum in two barriers: DPP/shuffle inside each wave, one LDS slot per wave, then every thread
 // adds the (at most 16) wave sums.  The finalize kernels below are latency bound -- one block per channel, a
@@ -330,38 +328,8 @@ bn_bwd_reduce_kernel(float *__restrict__ partial, const float *__restrict__ dy,
     }
 }
 
-__global__ void __launch_bounds__(256)
-bn_bwd_finalize_kernel(float *__restrict__ dgamma, float *__restrict__ dbeta,
-                       float *__restrict__ coef, const float *__restrict__ partial,
-                       const float *__restrict__ gamma, const float *__restrict__ invstd,
-                       int nblocks, int C, double nvox, int groups) {
-    const int c = blockIdx.x;
-    __shared__ double slots[256 / 64];
-    double dg_tot = 0.0, db_tot = 0.0;  // parameter gradients: summed over the statistic groups
-    for (int grp = 0; grp < groups; ++grp, partial += (size_t)nblocks * C * 2, invstd += C, coef += C * 3) {
-        double a = 0.0, b = 0.0;
-        for (int t = threadIdx.x; t < nblocks; t += 256) {
-            a += partial[((size_t)t * C + c) * 2 + 0];
-            b += partial[((size_t)t * C + c) * 2 + 1];
-        }
-        const double sa = bn_block_sum<256>(a, slots), sb = bn_block_sum<256>(b, slots);
-        if (threadIdx.x == 0) {
-            db_tot += sa;
-            dg_tot += sb;
-            // dx = k0 * (dz - k1 - xhat * k2)
-            coef[c * 3 + 0] = gamma[c] * invstd[c];
-            coef[c * 3 + 1] = (float)(sa / nvox);
-            coef[c * 3 + 2] = (float)(sb / nvox);
-        }
-    }
-    if (threadIdx.x == 0) {
-        dbeta[c] = (float)db_tot;
-        dgamma[c] = (float)dg_tot;
-    }
-}
-
-// `partial` given: the finalize step runs HERE, in every block's prologue, instead of in a kernel of its own -- the
-// reduce kernel then writes at most BN_BWD_PARTIAL_FLOATS floats of partials per statistic group (128 KB, L2-resident),
+// The finalize step runs HERE, in every block's prologue, instead of in a kernel of its own -- the
+// reduce kernel writes at most BN_BWD_PARTIAL_FLOATS floats of partials per statistic group (128 KB, L2-resident),
 // each block merges them (fp64 per thread, cross-lane, four waves through 2C floats of LDS) and block (0, g) also writes
 // coef / dgamma / dbeta.  One launch less per BatchNorm backward (85 per step), and the one that went away was a
 // 32-block kernel that, beside the other stream's matrix kernels, waited ~60 us for a free wave slot each time
@@ -398,90 +366,82 @@ bn_bwd_apply_kernel(float4 *__restrict__ dx, float4 *__restrict__ dz_out,
         smu[threadIdx.x] = mean[threadIdx.x];
         sis[threadIdx.x] = invstd[threadIdx.x];
     }
-    if (partial == nullptr) {
+    // one partial row = 2C floats = COLS float4; thread (r, j) sums column j of rows r, r + ROWS, ...
+    constexpr int COLS = C / 2, ROWS = 256 / COLS;
+    static_assert(COLS <= 64 && 64 % COLS == 0, "a partial row must tile a wave");
+    __shared__ float wsum[4][2 * C];
+    const int j = threadIdx.x % COLS, r = threadIdx.x / COLS, wave = threadIdx.x >> 6;
+    const bool writer = blockIdx.x == 0;
+    // block (0, 0) also needs the other groups' sums (dgamma / dbeta are summed over the groups)
+    const int g_lo = (writer && grp == 0) ? 0 : grp, g_hi = (writer && grp == 0) ? (int)gridDim.y : grp + 1;
+    double dg_tot = 0.0, db_tot = 0.0;
+    for (int g = g_lo; g < g_hi; ++g) {
+        const float4 *p4 = reinterpret_cast<const float4 *>(partial) + (size_t)g * nblocks * COLS;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        for (int blk = r; blk < nblocks; blk += ROWS) {
+            const float4 v = p4[(size_t)blk * COLS + j];
+            a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
+        }
+#pragma unroll
+        for (int off = COLS; off < 64; off <<= 1) {
+            a0 += __shfl_xor(a0, off); a1 += __shfl_xor(a1, off); a2 += __shfl_xor(a2, off); a3 += __shfl_xor(a3, off);
+        }
+        __syncthreads();  // wsum may still be read (previous group)
+        if ((threadIdx.x & 63) < COLS) {
+            wsum[wave][4 * j + 0] = (float)a0; wsum[wave][4 * j + 1] = (float)a1;
+            wsum[wave][4 * j + 2] = (float)a2; wsum[wave][4 * j + 3] = (float)a3;
+        }
+        __syncthreads();
         if (threadIdx.x < C) {
-            k0[threadIdx.x] = coef[threadIdx.x * 3 + 0];
-            k1[threadIdx.x] = coef[threadIdx.x * 3 + 1];
-            k2[threadIdx.x] = coef[threadIdx.x * 3 + 2];
-        }
-    } else {
-        // one partial row = 2C floats = COLS float4; thread (r, j) sums column j of rows r, r + ROWS, ...
-        constexpr int COLS = C / 2, ROWS = 256 / COLS;
-        static_assert(COLS <= 64 && 64 % COLS == 0, "a partial row must tile a wave");
-        __shared__ float wsum[4][2 * C];
-        const int j = threadIdx.x % COLS, r = threadIdx.x / COLS, wave = threadIdx.x >> 6;
-        const bool writer = blockIdx.x == 0;
-        // block (0, 0) also needs the other groups' sums (dgamma / dbeta are summed over the groups)
-        const int g_lo = (writer && grp == 0) ? 0 : grp, g_hi = (writer && grp == 0) ? (int)gridDim.y : grp + 1;
-        double dg_tot = 0.0, db_tot = 0.0;
-        for (int g = g_lo; g < g_hi; ++g) {
-            const float4 *p4 = reinterpret_cast<const float4 *>(partial) + (size_t)g * nblocks * COLS;
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-            for (int blk = r; blk < nblocks; blk += ROWS) {
-                const float4 v = p4[(size_t)blk * COLS + j];
-                a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
-            }
-#pragma unroll
-            for (int off = COLS; off < 64; off <<= 1) {
-                a0 += __shfl_xor(a0, off); a1 += __shfl_xor(a1, off); a2 += __shfl_xor(a2, off); a3 += __shfl_xor(a3, off);
-            }
-            __syncthreads();  // wsum may still be read (previous group)
-            if ((threadIdx.x & 63) < COLS) {
-                wsum[wave][4 * j + 0] = (float)a0; wsum[wave][4 * j + 1] = (float)a1;
-                wsum[wave][4 * j + 2] = (float)a2; wsum[wave][4 * j + 3] = (float)a3;
-            }
-            __syncthreads();
-            if (threadIdx.x < C) {
-                const int c = threadIdx.x;
-                const double sa = ((double)wsum[0][2 * c] + (double)wsum[1][2 * c]) + ((double)wsum[2][2 * c] + (double)wsum[3][2 * c]);
-                const double sb = ((double)wsum[0][2 * c + 1] + (double)wsum[1][2 * c + 1]) + ((double)wsum[2][2 * c + 1] + (double)wsum[3][2 * c + 1]);
-                db_tot += sa; dg_tot += sb;
-                if (g == grp) {  // dx = k0 * (dz - k1 - xhat * k2)
-                    k0[c] = gamma[c] * sis[c];
-                    k1[c] = (float)(sa / nvox);
-                    k2[c] = (float)(sb / nvox);
-                    if (writer) { coef[c * 3 + 0] = k0[c]; coef[c * 3 + 1] = k1[c]; coef[c * 3 + 2] = k2[c]; }
-                }
+            const int c = threadIdx.x;
+            const double sa = ((double)wsum[0][2 * c] + (double)wsum[1][2 * c]) + ((double)wsum[2][2 * c] + (double)wsum[3][2 * c]);
+            const double sb = ((double)wsum[0][2 * c + 1] + (double)wsum[1][2 * c + 1]) + ((double)wsum[2][2 * c + 1] + (double)wsum[3][2 * c + 1]);
+            db_tot += sa; dg_tot += sb;
+            if (g == grp) {  // dx = k0 * (dz - k1 - xhat * k2)
+                k0[c] = gamma[c] * sis[c];
+                k1[c] = (float)(sa / nvox);
+                k2[c] = (float)(sb / nvox);
+                if (writer) { coef[c * 3 + 0] = k0[c]; coef[c * 3 + 1] = k1[c]; coef[c * 3 + 2] = k2[c]; }
             }
         }
-        if (writer && grp == 0 && threadIdx.x < C) { dbeta[threadIdx.x] = (float)db_tot; dgamma[threadIdx.x] = (float)dg_tot; }
-        if (pmax) {  // (one statistic group only: az_bn3d_bwd rejects the combination otherwise)
-            const uint4 *m4 = reinterpret_cast<const uint4 *>(pmax);
-            uint4 m = make_uint4(0, 0, 0, 0);
-            for (int blk = r; blk < nblocks; blk += ROWS) {
-                const uint4 v = m4[(size_t)blk * COLS + j];
-                m.x = max(m.x, v.x); m.y = max(m.y, v.y); m.z = max(m.z, v.z); m.w = max(m.w, v.w);
-            }
-#pragma unroll
-            for (int off = COLS; off < 64; off <<= 1) {
-                m.x = max(m.x, (unsigned)__shfl_xor((int)m.x, off)); m.y = max(m.y, (unsigned)__shfl_xor((int)m.y, off));
-                m.z = max(m.z, (unsigned)__shfl_xor((int)m.z, off)); m.w = max(m.w, (unsigned)__shfl_xor((int)m.w, off));
-            }
-            __syncthreads();  // (k0 / k1 / k2 of every channel written; wsum free again)
-            if ((threadIdx.x & 63) < COLS) {
-                wsum[wave][4 * j + 0] = __uint_as_float(m.x); wsum[wave][4 * j + 1] = __uint_as_float(m.y);
-                wsum[wave][4 * j + 2] = __uint_as_float(m.z); wsum[wave][4 * j + 3] = __uint_as_float(m.w);
-            }
-            __syncthreads();
-            float bnd = 0.f;
-            if (threadIdx.x < C) {
-                const int c = threadIdx.x;
-                const float gm = fmaxf(fmaxf(wsum[0][2 * c], wsum[1][2 * c]), fmaxf(wsum[2][2 * c], wsum[3][2 * c]));
-                const float xm = fmaxf(fmaxf(wsum[0][2 * c + 1], wsum[1][2 * c + 1]), fmaxf(wsum[2][2 * c + 1], wsum[3][2 * c + 1]));
-                // (1 + 2^-20: the rounding of the apply expression itself)
-                bnd = fabsf(k0[c]) * (gm + fabsf(k1[c]) + xm * fabsf(k2[c])) * 1.000001f;
-                bnd = bnd < __builtin_inff() ? bnd : 0.f;  // (a non-finite coefficient: every element of that channel is, too)
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) bnd = fmaxf(bnd, __shfl_xor(bnd, off));
-            __shared__ float bwave[4];
-            if ((threadIdx.x & 63) == 0) bwave[wave] = bnd;
-            __syncthreads();
-            bnd = fmaxf(fmaxf(bwave[0], bwave[1]), fmaxf(bwave[2], bwave[3]));
-            split_scale = az_pow2(az_f16_scale_exp(bnd));
-            // slot 0 of the amax array (the reduce kernel zeroed all sixteen): the bound
-            if (writer && grp == 0 && threadIdx.x == 0 && amax) amax[0] = __float_as_uint(bnd);
+    }
+    if (writer && grp == 0 && threadIdx.x < C) { dbeta[threadIdx.x] = (float)db_tot; dgamma[threadIdx.x] = (float)dg_tot; }
+    if (pmax) {  // (one statistic group only: az_bn3d_bwd rejects the combination otherwise)
+        const uint4 *m4 = reinterpret_cast<const uint4 *>(pmax);
+        uint4 m = make_uint4(0, 0, 0, 0);
+        for (int blk = r; blk < nblocks; blk += ROWS) {
+            const uint4 v = m4[(size_t)blk * COLS + j];
+            m.x = max(m.x, v.x); m.y = max(m.y, v.y); m.z = max(m.z, v.z); m.w = max(m.w, v.w);
         }
+#pragma unroll
+        for (int off = COLS; off < 64; off <<= 1) {
+            m.x = max(m.x, (unsigned)__shfl_xor((int)m.x, off)); m.y = max(m.y, (unsigned)__shfl_xor((int)m.y, off));
+            m.z = max(m.z, (unsigned)__shfl_xor((int)m.z, off)); m.w = max(m.w, (unsigned)__shfl_xor((int)m.w, off));
+        }
+        __syncthreads();  // (k0 / k1 / k2 of every channel written; wsum free again)
+        if ((threadIdx.x & 63) < COLS) {
+            wsum[wave][4 * j + 0] = __uint_as_float(m.x); wsum[wave][4 * j + 1] = __uint_as_float(m.y);
+            wsum[wave][4 * j + 2] = __uint_as_float(m.z); wsum[wave][4 * j + 3] = __uint_as_float(m.w);
+        }
+        __syncthreads();
+        float bnd = 0.f;
+        if (threadIdx.x < C) {
+            const int c = threadIdx.x;
+            const float gm = fmaxf(fmaxf(wsum[0][2 * c], wsum[1][2 * c]), fmaxf(wsum[2][2 * c], wsum[3][2 * c]));
+            const float xm = fmaxf(fmaxf(wsum[0][2 * c + 1], wsum[1][2 * c + 1]), fmaxf(wsum[2][2 * c + 1], wsum[3][2 * c + 1]));
+            // (1 + 2^-20: the rounding of the apply expression itself)
+            bnd = fabsf(k0[c]) * (gm + fabsf(k1[c]) + xm * fabsf(k2[c])) * 1.000001f;
+            bnd = bnd < __builtin_inff() ? bnd : 0.f;  // (a non-finite coefficient: every element of that channel is, too)
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) bnd = fmaxf(bnd, __shfl_xor(bnd, off));
+        __shared__ float bwave[4];
+        if ((threadIdx.x & 63) == 0) bwave[wave] = bnd;
+        __syncthreads();
+        bnd = fmaxf(fmaxf(bwave[0], bwave[1]), fmaxf(bwave[2], bwave[3]));
+        split_scale = az_pow2(az_f16_scale_exp(bnd));
+        // slot 0 of the amax array (the reduce kernel zeroed all sixteen): the bound
+        if (writer && grp == 0 && threadIdx.x == 0 && amax) amax[0] = __float_as_uint(bnd);
     }
     __syncthreads();
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += gridDim.x * 256LL) {
@@ -594,11 +554,7 @@ sum4_kernel(float4 *__restrict__ y, const float4 *__restrict__ a, const float4 *
 }
 
 #define BN_GRID(total) az_grid_for((total), 256)
-// finalize folded into the apply kernel's prologue (AZ_BN_BWD_FUSED=0: the three-kernel sequence, for A/B runs)
-static bool bn_bwd_fused() {
-    const int on = az_options().bn_bwd_fused;
-    return on != 0;
-}
+// reduce blocks of a BatchNorm backward (the finalize step is folded into the apply kernel's prologue)
 static int bn_bwd_fused_blocks(int blocks, int C) {
     const int cap = BN_BWD_PARTIAL_FLOATS / (2 * C);  // 512 / 256 / 128 reduce blocks for 32 / 64 / 128 channels
     return blocks < cap ? blocks : cap;
@@ -700,22 +656,13 @@ extern "C" int az_bn3d_bwd(float *dx, float *dz_out, float *dgamma, float *dbeta
     const long long total4 = nvox * C / 4;
     hipStream_t s = az_stream(stream);
     const bool nt = total4 * 16 >= BN_NT_BYTES;
-    if (split_out && (!am || !bn_bwd_fused())) return split_out && !am ? AZ_ENULL : AZ_EUNSUPPORTED;  // (the fused two-launch form only)
-    if (bn_bwd_fused()) {
-        blocks = bn_bwd_fused_blocks(blocks, C);
-        unsigned *const pmax = split_out ? reinterpret_cast<unsigned *>(workspace) + (size_t)blocks * C * 2 : nullptr;
-        BN_LAUNCH(bn_bwd_reduce_kernel, C, nt, dim3(blocks), s, workspace, dy, y, x, mean, invstd, scale, shift, relu, nvox, am, pmax);
-        BN_LAUNCH(bn_bwd_apply_kernel, C, nt, dim3(bn_bwd_apply_grid(total4)), s, (float4 *)dx, (float4 *)dz_out, (const float4 *)dy,
-                  (const float4 *)y, (const float4 *)x, mean, invstd, coef, scale, shift, relu, total4,
-                  (const float *)workspace, blocks, gamma, dgamma, dbeta, (double)nvox, am, (const unsigned *)pmax);
-        return az_launch_status();
-    }
-    BN_LAUNCH(bn_bwd_reduce_kernel, C, nt, dim3(blocks), s, workspace, dy, y, x, mean, invstd, scale, shift, relu, nvox, am);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, dgamma, dbeta, coef,
-                       workspace, gamma, invstd, blocks, C, (double)nvox, 1);
-    BN_LAUNCH(bn_bwd_apply_kernel, C, nt, dim3(BN_GRID(total4)), s, (float4 *)dx, (float4 *)dz_out, (const float4 *)dy,
+    if (split_out && !am) return AZ_ENULL;
+    blocks = bn_bwd_fused_blocks(blocks, C);
+    unsigned *const pmax = split_out ? reinterpret_cast<unsigned *>(workspace) + (size_t)blocks * C * 2 : nullptr;
+    BN_LAUNCH(bn_bwd_reduce_kernel, C, nt, dim3(blocks), s, workspace, dy, y, x, mean, invstd, scale, shift, relu, nvox, am, pmax);
+    BN_LAUNCH(bn_bwd_apply_kernel, C, nt, dim3(bn_bwd_apply_grid(total4)), s, (float4 *)dx, (float4 *)dz_out, (const float4 *)dy,
               (const float4 *)y, (const float4 *)x, mean, invstd, coef, scale, shift, relu, total4,
-              (const float *)nullptr, 0, gamma, dgamma, dbeta, (double)nvox, am);
+              (const float *)workspace, blocks, gamma, dgamma, dbeta, (double)nvox, am, (const unsigned *)pmax);
     return az_launch_status();
 }
 
@@ -764,8 +711,8 @@ extern "C" int az_bn3d_stats(float *partials, float *counts, const float *x, lon
 }
 
 // ---- grouped BatchNorm of a channels-last tensor [groups][nvox][C] (the extractor's layers) ------
-// One call = statistics + finalize + apply (forward) or reduce + finalize + apply (backward) for ALL
-// statistic groups: three launches per layer instead of six per group.
+// One call = statistics + finalize + apply (forward) or reduce + apply (backward) for ALL
+// statistic groups: three / two launches per layer instead of six per group.
 static int bn2d_blocks(long long nvox, int C) {
     const int vpb = 256 / (C / 4);
     return (int)az_grid_for((nvox + vpb - 1) / vpb * 256, 256);
@@ -832,22 +779,12 @@ static void bn2d_bwd_launch(float *dx, float *dz, float *dgamma, float *dbeta, f
     int blocks = bn2d_blocks(nvox, C);
     float *partial = ws, *coef = ws + (size_t)groups * blocks * C * 2;  // (coef behind the UNCAPPED partial area)
     const long long total4 = nvox * C / 4;
-    if (bn_bwd_fused()) {
-        blocks = bn_bwd_fused_blocks(blocks, C);
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<C, false>), dim3(blocks, groups), dim3(256), 0, s, partial, dy, y, x, mean,
-                           invstd, scale, shift, relu, nvox);
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<C, false>), dim3(bn_bwd_apply_grid(total4), groups), dim3(256), 0, s, (float4 *)dx,
-                           (float4 *)dz, (const float4 *)dy, (const float4 *)y, (const float4 *)x, mean, invstd,
-                           coef, scale, shift, relu, total4, (const float *)partial, blocks, gamma, dgamma, dbeta, (double)nvox, amax);
-        return;
-    }
+    blocks = bn_bwd_fused_blocks(blocks, C);
     hipLaunchKernelGGL((bn_bwd_reduce_kernel<C, false>), dim3(blocks, groups), dim3(256), 0, s, partial, dy, y, x, mean,
                        invstd, scale, shift, relu, nvox);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, dgamma, dbeta, coef, partial, gamma,
-                       invstd, blocks, C, (double)nvox, groups);
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<C, false>), dim3(BN_GRID(total4), groups), dim3(256), 0, s, (float4 *)dx,
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<C, false>), dim3(bn_bwd_apply_grid(total4), groups), dim3(256), 0, s, (float4 *)dx,
                        (float4 *)dz, (const float4 *)dy, (const float4 *)y, (const float4 *)x, mean, invstd,
-                       coef, scale, shift, relu, total4, (const float *)nullptr, 0, gamma, dgamma, dbeta, (double)nvox);
+                       coef, scale, shift, relu, total4, (const float *)partial, blocks, gamma, dgamma, dbeta, (double)nvox, amax);
 }
 
 /* backward of az_bn2d_fwd; dgamma/dbeta [C] are summed over the groups; dz_out may be NULL */

@@ -13,8 +13,8 @@
 //     registers): an A fragment read from LDS feeds every N tile (12 / 24 MFMAs) -- with one N tile per wave, as in the
 //     3-D kernel where the three kd share the fragment, a 2-D stage would need 3 KB of LDS reads per 96 matrix cycles
 //     on every SIMD: all of the LDS bandwidth -- and the slab is staged once per patch whatever the channel count
-//     (AZ_CONV2D_ROLL_NT4=0: 64 channels as two workgroups per patch, for A/B runs: 104 vs 102 us alone, 0.106 /
-//     0.123 vs 0.098 / 0.111 ms forward / input gradient in the step);
+//     (measured against 64 channels as two workgroups per patch: 102 vs 104 us alone, 0.098 / 0.111 vs 0.106 /
+//     0.123 ms forward / input gradient in the step);
 //   * BatchNorm partials (EPI 1): per-lane running sums about a per-lane shift, one row per (wave quarter, group
 //     segment), in az_bn2d_fwd's layout [group][cout][rows][2] / [group][rows].
 // Arithmetic: az_common.h's bf16x6 product; accumulation order per output: 32-channel chunk, kh, kw.
@@ -22,7 +22,6 @@
 #include <type_traits>
 
 #include "az_roll_common.h"
-#include "az_options.h"
 #include "az_launch_math.h"
 
 struct C2RArgs {
@@ -681,24 +680,21 @@ extern "C" long long az_conv2d_roll_stats_rows(int groups, int B, int H, int W, 
     return a.rows;
 }
 
-// AZ_CONV2D_ROLL_NT4=0: 64 output channels as two channel groups in the grid (two workgroups per patch, each staging
-// the slab) instead of four N tiles per wave
-static bool c2r_nt4() {
-    const int on = az_options().conv2d_roll_nt4;
-    return on != 0;
-}
+// one workgroup per (patch, image segment) whatever the channel count: 64 output channels are four N tiles per wave
+// (bf16x6) or the 3-D kernel's wave layout (f16x3, conv2d_roll64_kernel), 32 are two N tiles per wave
 template <int EPI, int AR = 0>
 static int c2r_launch(const C2RArgs &a, int cin, hipStream_t s) {
-    const bool nt4 = a.cout == 64 && c2r_nt4();
-    const long long blocks = (long long)a.G * a.nseg * a.tiles_yb * a.tiles_x * (nt4 ? 1 : a.cout / 32);
+    const long long blocks = (long long)a.G * a.nseg * a.tiles_yb * a.tiles_x;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return AZ_EUNSUPPORTED;
     const dim3 grid((unsigned)blocks), blk(256);
-    if (nt4 && AR == 1 && az_options().conv2d_roll_h) {  // f16x3, 64 output channels: the 3-D kernel's wave layout
-        if (cin == 32) hipLaunchKernelGGL((conv2d_roll64_kernel<32, EPI>), grid, blk, 0, s, a);
-        else hipLaunchKernelGGL((conv2d_roll64_kernel<64, EPI>), grid, blk, 0, s, a);
-    } else if (nt4) {
-        if (cin == 32) hipLaunchKernelGGL((conv2d_roll_kernel<32, EPI, 4, AR>), grid, blk, 0, s, a);
-        else hipLaunchKernelGGL((conv2d_roll_kernel<64, EPI, 4, AR>), grid, blk, 0, s, a);
+    if (a.cout == 64) {
+        if constexpr (AR == 1) {
+            if (cin == 32) hipLaunchKernelGGL((conv2d_roll64_kernel<32, EPI>), grid, blk, 0, s, a);
+            else hipLaunchKernelGGL((conv2d_roll64_kernel<64, EPI>), grid, blk, 0, s, a);
+        } else {
+            if (cin == 32) hipLaunchKernelGGL((conv2d_roll_kernel<32, EPI, 4, AR>), grid, blk, 0, s, a);
+            else hipLaunchKernelGGL((conv2d_roll_kernel<64, EPI, 4, AR>), grid, blk, 0, s, a);
+        }
     } else {
         if (cin == 32) hipLaunchKernelGGL((conv2d_roll_kernel<32, EPI, 2, AR>), grid, blk, 0, s, a);
         else hipLaunchKernelGGL((conv2d_roll_kernel<64, EPI, 2, AR>), grid, blk, 0, s, a);

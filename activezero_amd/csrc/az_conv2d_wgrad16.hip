@@ -19,7 +19,6 @@
 #include <stdlib.h>
 
 #include "az_roll_common.h"
-#include "az_options.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -254,7 +253,7 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
 // atomics, which the memory side retires in ~35 us whatever produced them (the kernel above: 768 workgroups x 9 x 32 x 32 = 7.1 M):
 // BOTH kernels are flush-bound at this size, not LDS- or MFMA-bound.  In the step these launches sit on the side stream with
 // ~25 ms of slack, so the flush costs chip contention, not wall time; kept as the default for its lighter LDS / VALU footprint
-// beside the main stream's kernels (same-box step A/B 86.28 vs 86.43 ms), AZ_CONV2D_WGRAD_W64=0 restores the 2 x 2 tiles.
+// beside the main stream's kernels (same-box step A/B 86.28 vs 86.43 ms).
 #define X16_CIMG (2 * 32 * V16_ROWB)            // one 32-channel dy image: [part][k = 32][32 ch]            4 096 B
 #define X16_CBUF (2 * X16_CIMG)                 // both channel halves                                        8 192 B
 #define X16_FIMG (2 * V16_FW * V16_ROWB)        // one 32-channel x row image: [part][18 positions][32 ch]   2 304 B
@@ -476,8 +475,8 @@ int az_conv2d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine
     a.nrseg = best_seg;
     a.ncols = (long long)B * a.nwchunk * a.nrseg;
     a.wgs = best_w;
-    if (coarse_amax && fine_amax && cm == 64 && cn == 64 && az_options().conv2d_wgrad_w64) {
-        // one 64 x 64 tile per workgroup of eight waves, one workgroup per CU (AZ_CONV2D_WGRAD_W64=0: 2 x 2 tiles on the kernel above)
+    if (coarse_amax && fine_amax && cm == 64 && cn == 64) {
+        // one 64 x 64 tile per workgroup of eight waves, one workgroup per CU
         int best_seg2 = 1, best_w2 = 1;
         double best2 = -1.0;
         for (int nseg = 1; nseg <= 16; ++nseg) {

@@ -213,11 +213,10 @@ typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 
 #define X6_WCH 16  // coarse positions per chunk = one K16 block
 
-#define WGX6_S2_WAVES(S) ((S) == 1 ? 2 : 1)
-// AR: 0 = bf16x6, 1 = f16x3 (two scaled fp16 parts, three MFMAs per tap; az_roll_common.h) -- the LDS images keep their
-// three-part strides, the third part is then unused
+// AR: 0 = bf16x6 (stride 2 only: stride 1 runs conv3d_wgrad_x6_fw_kernel below), 1 = f16x3 (two scaled fp16 parts, three
+// MFMAs per tap; az_roll_common.h) -- the LDS images keep their three-part strides, the third part is then unused
 template <int CM, int CN, int S, int AR = 0>
-__global__ void __launch_bounds__(64, AR ? 2 : WGX6_S2_WAVES(S))
+__global__ void __launch_bounds__(64, AR ? 2 : 1)
 conv3d_wgrad_x6_kernel(const WgArgs a) {
     constexpr int WCH = X6_WCH;
     constexpr int NP = AR ? 2 : 3;
@@ -592,12 +591,11 @@ static int launch_wgrad(WgArgs a, hipStream_t s) {
     a.nitems = base_items * a.nhseg;
     if (a.nitems < a.waves_per_combo) a.waves_per_combo = (int)((a.nitems + 7) & ~7LL);
     a.order = az_options().wgrad_order;
-    const int fine_walk = az_options().wgrad_fw;  // AZ_WGRAD_FW=0: the coarse-row walk for the stride-1 layers too (A/B)
-    if (PREC == 3)
+    if constexpr (PREC == 3)
         hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<CM, CN, S, 1>), dim3(a.waves_per_combo * NCOMBO), dim3(64), 0, s, a);
-    else if (PREC == 1 && S == 1 && fine_walk)
+    else if constexpr (PREC == 1 && S == 1)  // bf16x6, stride 1: the fine-row walk
         hipLaunchKernelGGL((conv3d_wgrad_x6_fw_kernel<CM, CN>), dim3(a.waves_per_combo * NCOMBO), dim3(64), 0, s, a);
-    else if (PREC == 1)
+    else if constexpr (PREC == 1)
         hipLaunchKernelGGL((conv3d_wgrad_x6_kernel<CM, CN, S>), dim3(a.waves_per_combo * NCOMBO),
                            dim3(64), 0, s, a);
     else

@@ -23,14 +23,10 @@
 // per part: LDS holds [part][row][32 k] bf16 with an 80-byte row pitch (16 lanes of a fragment read cover the 64
 // banks once).  Chunk s+1 travels global -> registers under the MFMAs of chunk s; one 30 KB buffer, so that five
 // workgroups share a CU: the kernel is bound by HBM latency, which occupancy hides and a one-chunk prefetch does not.  (Rounds 1-2 ran these GEMMs on v_mfma_f32_32x32x2_f32 with scalar LDS
-// staging: 0.45 ms for the volume at [4,256,136,240], 11 % of its HBM bound; bgemm_tn_kernel is kept for
-// AZ_CORR_FP32=1.)
+// staging: 0.45 ms for the volume at [4,256,136,240], 11 % of its HBM bound.)
 #include <stdlib.h>
 
 #include "az_common.h"
-#include "az_options.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct GemmArgs {
     const float *A, *B;
@@ -45,53 +41,6 @@ struct GemmArgs {
 #define G_TN 64
 #define G_TK 32
 
-__global__ void __launch_bounds__(256)
-bgemm_tn_kernel(const GemmArgs g) {
-    __shared__ float sA[G_TK][G_TM + 1];
-    __shared__ float sB[G_TK][G_TN + 1];
-    const int batch = blockIdx.z;
-    const int b = batch / g.H, h = batch - b * g.H;
-    const float *A = g.A + b * g.bA0 + h * g.bA1;
-    const float *B = g.B + b * g.bB0 + h * g.bB1;
-    float *D = g.D + b * g.bD0 + h * g.bD1;
-    const int m0 = blockIdx.y * G_TM, n0 = blockIdx.x * G_TN;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int row = lane & 31, half = lane >> 5;
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    // staging order: make the unit-stride index the fastest-varying one across threads
-    const bool a_m_fast = g.sAm <= g.sAk, b_n_fast = g.sBn <= g.sBk;
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    for (int k0 = 0; k0 < g.K; k0 += G_TK) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < G_TK * G_TM; e += 256) {
-            const int kk = a_m_fast ? e / G_TM : e % G_TK;
-            const int mm = a_m_fast ? e % G_TM : e / G_TK;
-            const int k = k0 + kk, m = m0 + mm;
-            sA[kk][mm] = (k < g.K && m < g.M) ? A[k * g.sAk + m * g.sAm] : 0.f;
-        }
-        for (int e = threadIdx.x; e < G_TK * G_TN; e += 256) {
-            const int kk = b_n_fast ? e / G_TN : e % G_TK;
-            const int nn = b_n_fast ? e % G_TN : e / G_TK;
-            const int k = k0 + kk, n = n0 + nn;
-            sB[kk][nn] = (k < g.K && n < g.N) ? B[k * g.sBk + n * g.sBn] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < G_TK / 2; ++q)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sA[2 * q + half][wm + row],
-                                                       sB[2 * q + half][wn + row], acc, 0, 0, 0);
-    }
-    const int n = n0 + wn + row;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (m < g.M && n < g.N) D[m * g.sDm + n * g.sDn] = acc[r] * g.scale;
-    }
-}
-
-// ---- bf16x6 version -------------------------------------------------------------------------------------
 #define GX_PITCH 80                      // bytes per (row, part): 32 k x bf16 + 16 pad
 #define GX_PART (G_TM * GX_PITCH)        // one part of one operand tile
 #define GX_OPER (3 * GX_PART)            // one operand tile: 15 360 B
@@ -207,11 +156,6 @@ bgemm_x6_kernel(const GemmArgs g) {
 static int launch_gemm(const GemmArgs &g, int batches, hipStream_t s) {
     if (batches <= 0 || batches > 65535) return AZ_EUNSUPPORTED;
     dim3 grid((g.N + G_TN - 1) / G_TN, (g.M + G_TM - 1) / G_TM, batches);
-    const int fp32 = az_options().corr_fp32;
-    if (fp32) {
-        hipLaunchKernelGGL(bgemm_tn_kernel, grid, dim3(256), 0, s, g);
-        return az_launch_status();
-    }
     const bool ak = g.sAk == 1 && g.sAm != 1, bk = g.sBk == 1 && g.sBn != 1;
     if (ak && bk) hipLaunchKernelGGL((bgemm_x6_kernel<true, true>), grid, dim3(256), 0, s, g);
     else if (ak) hipLaunchKernelGGL((bgemm_x6_kernel<true, false>), grid, dim3(256), 0, s, g);

@@ -162,7 +162,7 @@ patch_reproj_kernel(double *__restrict__ acc, float *__restrict__ gdisp,
 // every image row is read (TR + 2r + 2) / TR times from L2 instead of (ps+1)^2 times from L1.
 // Shapes whose bands do not fit in 160 KB of LDS (W > ~1000 at ps = 11) keep the per-pixel kernel.
 // PSM: compile-time bound of ps (register arrays), PR_K: pixels per thread (4 forward; 2 backward, which also carries
-// the derivative rows)
+// the derivative rows; one pixel per thread measured the same forward time and a slower backward)
 template <int MODE, int PSM, int PR_K>
 __global__ void __launch_bounds__(512)
 patch_reproj_tiled_kernel(double *__restrict__ acc, float *__restrict__ gdisp, const float *__restrict__ gloss,
@@ -311,22 +311,11 @@ static int pr_band_rows(int B, int H, int W, int ps, int pr_k, size_t *lds_bytes
     return best;
 }
 static bool pr_tiled_enabled() { return az_options().patch_tiled != 0; }
-template <int MODE, int PSM, int K>
-static bool pr_launch_tiled_k(double *acc, float *gdisp, const float *gloss, const float *L, const float *R,
-                              const float *disp, const uint8_t *mask, int B, int C, int H, int W, int ps, float sign,
-                              hipStream_t s);
 template <int MODE, int PSM>
 static bool pr_launch_tiled_ps(double *acc, float *gdisp, const float *gloss, const float *L, const float *R,
                                const float *disp, const uint8_t *mask, int B, int C, int H, int W, int ps, float sign,
                                hipStream_t s) {
-    const int kk = az_options().patch_k;  // 1: one pixel per thread (A/B: same forward time, slower backward)
-    if (kk == 1) return pr_launch_tiled_k<MODE, PSM, 1>(acc, gdisp, gloss, L, R, disp, mask, B, C, H, W, ps, sign, s);
-    return pr_launch_tiled_k<MODE, PSM, (MODE == 0 ? 4 : 2)>(acc, gdisp, gloss, L, R, disp, mask, B, C, H, W, ps, sign, s);
-}
-template <int MODE, int PSM, int K>
-static bool pr_launch_tiled_k(double *acc, float *gdisp, const float *gloss, const float *L, const float *R,
-                              const float *disp, const uint8_t *mask, int B, int C, int H, int W, int ps, float sign,
-                              hipStream_t s) {
+    constexpr int K = MODE == 0 ? 4 : 2;
     size_t lds = 0;
     const int tr = pr_band_rows(B, H, W, ps, K, &lds);
     if (tr <= 0) return false;

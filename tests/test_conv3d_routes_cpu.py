@@ -71,7 +71,7 @@ class _Lib:
         self.s2roll_on, self.split_ok = s2roll_on, split_ok
 
     def az_option(self, name):
-        return {b"AZ_CONV_S2ROLL": int(self.s2roll_on), b"AZ_BN_BWD_FUSED": 1}[name]
+        return {b"AZ_CONV_S2ROLL": int(self.s2roll_on)}[name]
 
     def az_conv3d_fwd_f16_split_ok(self, *a):
         return self.split_ok

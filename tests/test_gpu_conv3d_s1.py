@@ -101,7 +101,7 @@ def route(kind, cin, cout, arith, shape, split_mask=0):
         if arith == "f16x3":
             assert conv3d._f16_wgrad_ok(conv3d.CONV_S1, cin, cout)
             assert lib().az_conv3d_wgrad_f16_split_ok(1, b, cm, cn, d, h, w, d, h, w) == 3  # (= the r16 kernel takes it)
-            name = "r16 AR1" + (" wide" if opt("AZ_WGRAD_R16_WIDE") else "") + f" mask {split_mask}"
+            name = f"r16 AR1 mask {split_mask}"
         else:
             assert split_mask == 0
             name = "r16 AR0"
@@ -114,7 +114,7 @@ def route(kind, cin, cout, arith, shape, split_mask=0):
         return name
     assert split_mask == 0
     if arith == "bf16x6":
-        return "one-kd bf16x6" + (" fw" if opt("AZ_WGRAD_FW") else "")
+        return "one-kd bf16x6 fw"
     return "one-kd fp32"
 
 
@@ -128,9 +128,8 @@ def test_every_route_of_the_family_is_swept():
     want += ["roll2 f16x3", "roll2 f16x3 presplit"] if opt("AZ_CONV_ROLL64") else []
     want += [f"mask {m}" for m in range(4)]
     want += ["roll bf16x6" if conv3d._ROLL else ("m128 bf16x6" if opt("AZ_CONV_M128") else "gather bf16x6"), "gather bf16x6"]
-    want += ["r16 AR0"] if opt("AZ_WGRAD_R16") else ["one-kd bf16x6" + (" fw" if opt("AZ_WGRAD_FW") else "")]
+    want += ["r16 AR0"] if opt("AZ_WGRAD_R16") else ["one-kd bf16x6 fw"]
     want += ["xcd"] if opt("AZ_WGRAD_R16_XCD") and opt("AZ_WGRAD_R16_WGS") % 8 == 0 else []
-    want += ["wide"] if opt("AZ_WGRAD_R16_WIDE") else []
     missing = [n for n in want if not any(n in r for r in names)]
     assert not missing, (missing, sorted(names))
 

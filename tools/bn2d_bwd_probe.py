@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """az_bn2d_bwd / az_bn3d_bwd alone on the tensors of the step that are NOT V0-sized (the 2-D extractor's, the 1/8-resolution
-64-channel volume): ms per call and TB/s over the five tensor passes.  AZ_BN_BWD_FUSED=0 for the three-kernel sequence."""
+64-channel volume): ms per call and TB/s over the five tensor passes."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from activezero_amd import _lib
@@ -54,7 +54,6 @@ def run3d(shape, relu):
     print(f"bn3d_bwd {shape} relu={relu}: {ms * 1e3:7.1f} us  {gb / ms:5.2f} TB/s over 5 passes ({gb * 1e3:.0f} MB)")
 
 
-print("AZ_BN_BWD_FUSED =", os.environ.get("AZ_BN_BWD_FUSED", "1 (default)"))
 run2d(2, 4 * 136 * 240, 64, True)
 run2d(2, 4 * 136 * 240, 64, False)
 run2d(2, 4 * 136 * 240, 128, True)

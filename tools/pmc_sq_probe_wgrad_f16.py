@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """three launches of the f16x3 V0 weight gradient (B = 4, 48 x 136 x 240, 32 -> 32) for the SQ counter passes of
-tools/pmc_stall_passes.sh (PROBE=pmc_sq_probe_wgrad_f16.py; AZ_WGRAD_R16_WIDE selects the kernel)"""
+tools/pmc_stall_passes.sh (PROBE=pmc_sq_probe_wgrad_f16.py)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from activezero_amd import conv3d

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """f16x3 weight gradient of the 2-D 3x3 layers alone (B = 8 images: left + right of 4 pairs): 64 -> 64 at 136 x 240 (layer2) and
-32 -> 32 at 272 x 480 (firstconv / layer1); HIP events over 20 launches behind 10.  AZ_CONV2D_WGRAD_W64 selects the 64 x 64-tile kernel."""
+32 -> 32 at 272 x 480 (firstconv / layer1); HIP events over 20 launches behind 10.
+The 64 -> 64 shape runs the 64 x 64-tile kernel, the 32 -> 32 shape the 32 x 32-tile one."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from activezero_amd import _lib, amax, conv2d
 dev = torch.device("cuda:0")
-print("AZ_CONV2D_WGRAD_W64 =", _lib.lib().az_option(b"AZ_CONV2D_WGRAD_W64"))
 for c, (h, w) in ((64, (136, 240)), (32, (272, 480))):
     xr = torch.randn(8, h, w, c, device=dev).relu_()
     gr = torch.randn(8, h, w, c, device=dev) * 1e-4
