@@ -19,6 +19,7 @@
 
 #include "az_roll_common.h"
 #include "az_options.h"
+#include "az_launch_math.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -267,33 +268,12 @@ static int launch_w2(W2Args a, hipStream_t s) {
     const bool plain = a.plain_bf16 != 0;
     const int ncombo = (a.CM / (32 * MT)) * (a.CN / (32 * NT));
     a.nwchunk = (a.W + W2_WCH - 1) / W2_WCH;
-    // Static work lists (as az_conv3d_wgrad.hip): block w of a combo takes items w, w + Wb, ...; the kernel
-    // ends with its most loaded block, so pick (row segments, blocks per combo) with the item count a
-    // near multiple of the block count while ncombo * Wb * MT*NT stays close to the resident waves.
-    const int slots = 256 * 8 / (MT * NT);  // resident workgroups at 2 waves/SIMD
-    const int wmax = max(8, (slots / ncombo) & ~7);
-    const long long base_items = (long long)a.B * a.nwchunk;
-    double best = -1.0;
-    int best_w = 8, best_rows = a.H;
-    constexpr int R = DIL * (KH - 1) + 1;
-    for (int nseg = 1; nseg <= min(a.H, 32); ++nseg) {
-        const int rows = (a.H + nseg - 1) / nseg;
-        const int segs = (a.H + rows - 1) / rows;
-        const long long items = base_items * segs;
-        for (int w = wmax; w >= max(8, wmax / 2); w -= 8) {
-            const long long per = (items + w - 1) / w;
-            const double balance = (double)items / (double)(per * w);
-            const double occ = (double)w / (double)wmax;
-            const double amort = (double)rows / (double)(rows + R - 1 + 2);  // ring prologue per item
-            const double score = balance * (0.5 + 0.5 * occ) * amort;
-            if (score > best) { best = score; best_w = w; best_rows = rows; }
-        }
-    }
-    a.blocks_per_combo = best_w;
-    a.hseg_rows = best_rows;
-    a.nhseg = (a.H + a.hseg_rows - 1) / a.hseg_rows;
-    a.nitems = base_items * a.nhseg;
-    if (a.nitems < a.blocks_per_combo) a.blocks_per_combo = (int)((a.nitems + 7) & ~7LL);
+    // static work lists (block w of a combo takes items w, w + Wb, ...): az_launch_math.h az_c2w_plan
+    const AzC2wPlan p = az_c2w_plan(a.B, a.H, a.W, MT, NT, ncombo, DIL * (KH - 1) + 1);
+    a.blocks_per_combo = p.blocks_per_combo;
+    a.hseg_rows = p.hseg_rows;
+    a.nhseg = p.nhseg;
+    a.nitems = p.nitems;
     if (plain) {
         if constexpr (KH == 3 && KW == 3 && DIL == 1) {  // (the GRU's convolutions: the only users)
             if (a.plain_bf16 == 2)
@@ -325,6 +305,11 @@ static int dispatch_tiles(const W2Args &a, hipStream_t s) {
 int az_conv2d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine, int B, int H, int W, int cm, int cn,
                                int cs_c, int cs_f, hipStream_t s, const float *coarse_amax, const float *fine_amax);
 
+// the 3x3 d1 layers with 32 / 64 channels on either side go to az_conv2d_wgrad16.hip (AZ_CONV2D_WGRAD_R16=0: off)
+static bool wgrad2d_on_r16(int cm, int cn, int kh, int kw, int dilation) {
+    return kh == 3 && kw == 3 && dilation == 1 && az_options().conv2d_wgrad_r16 && (cm == 32 || cm == 64) && (cn == 32 || cn == 64);
+}
+
 extern "C" long long az_conv2d_wgrad_workspace(int cm, int cn, int kh, int kw) {
     if (cm <= 0 || cn <= 0 || cm % 32 || cn % 32 || kh <= 0 || kw <= 0) return AZ_EINVAL;
     return (long long)kh * kw * cm * cn * (long long)sizeof(float);
@@ -353,8 +338,7 @@ static int conv2d_wgrad_impl(float *grad_w, float *workspace, long long workspac
     a.plain_bf16 = plain_bf16;
     a.B = B; a.H = H; a.W = W; a.CM = cm; a.CN = cn; a.cs_c = go_cstride; a.cs_f = in_cstride;
     int rc = AZ_EUNSUPPORTED;
-    const int r16 = az_options().conv2d_wgrad_r16;
-    if (kh == 3 && kw == 3 && dilation == 1 && r16 && !plain_bf16 && (cm == 32 || cm == 64) && (cn == 32 || cn == 64))
+    if (wgrad2d_on_r16(cm, cn, kh, kw, dilation) && !plain_bf16)
         rc = az_conv2d_wgrad_r16_launch(workspace, grad_out, in, B, H, W, cm, cn, go_cstride, in_cstride, s, go_amax, in_amax);  // az_conv2d_wgrad16.hip
     else if (kh == 3 && kw == 3 && dilation == 1) rc = dispatch_tiles<3, 3, 1>(a, s);
     else if (kh == 3 && kw == 3 && dilation == 2) rc = dispatch_tiles<3, 3, 2>(a, s);
@@ -390,6 +374,34 @@ extern "C" int az_conv2d_wgrad_f16(float *grad_w, float *workspace, long long wo
     AZ_REQUIRE_PTR(go_amax); AZ_REQUIRE_PTR(in_amax);
     return conv2d_wgrad_impl(grad_w, workspace, workspace_bytes, grad_out, in, go_amax, in_amax, B, H, W, cm, cn, cm_real,
                              cn_real, go_cstride, in_cstride, kh, kw, dilation, stream);
+}
+
+/* the kernel and launch plan az_conv2d_wgrad (f16 = 0) / az_conv2d_wgrad_f16 (f16 = 1) take for this shape under the current
+ * switches, from the functions the launches call (az_launch_math.h) */
+extern "C" int az_conv2d_wgrad_plan(long long *plan, int f16, int B, int H, int W, int cm, int cn, int kh, int kw, int dilation) {
+    AZ_REQUIRE_PTR(plan);
+    AZ_REQUIRE(B > 0 && H > 0 && W > 0);
+    if (az_conv2d_wgrad_workspace(cm, cn, kh, kw) < 0) return AZ_EUNSUPPORTED;
+    for (int i = 0; i < 8; ++i) plan[i] = 0;
+    if (wgrad2d_on_r16(cm, cn, kh, kw, dilation)) {
+        const int ntiles = (cm / 32) * (cn / 32);
+        const bool w64 = f16 && cm == 64 && cn == 64;
+        const int slots = w64 ? 256 : 256 * 3 / ntiles;
+        const AzC2w16Plan p = az_c2w16_plan(B, H, W, slots);
+        plan[0] = w64 ? AZ_C2W_KERNEL_W64 : f16 ? AZ_C2W_KERNEL_R16_AR1 : AZ_C2W_KERNEL_R16_AR0;
+        plan[1] = p.seg_rows; plan[2] = p.nrseg; plan[3] = p.ncols; plan[4] = p.wgs; plan[5] = slots;
+        return AZ_OK;
+    }
+    int kh_l = kh, launches = 1;  // rows of taps per launch
+    if (kh == 3 && kw == 5 && dilation == 1) { kh_l = 1; launches = 3; }
+    else if (!((kh == 3 && kw == 3 && (dilation == 1 || dilation == 2)) || (kh == 1 && kw == 1))) return AZ_EUNSUPPORTED;
+    if (kh == 1) dilation = 1;
+    const int mt = (cm % 64) == 0 ? 2 : 1, nt = (cn % 64) == 0 ? 2 : 1;  // dispatch_tiles
+    const AzC2wPlan p = az_c2w_plan(B, H, W, mt, nt, (cm / (32 * mt)) * (cn / (32 * nt)), dilation * (kh_l - 1) + 1);
+    plan[0] = AZ_C2W_KERNEL_GENERIC;
+    plan[1] = mt; plan[2] = nt; plan[3] = p.blocks_per_combo; plan[4] = p.hseg_rows; plan[5] = p.nhseg; plan[6] = p.nitems;
+    plan[7] = launches;
+    return AZ_OK;
 }
 
 /* az_conv2d_wgrad_bf16 with ONE FP16 part per operand ("f16x1", az_conv2d_h1_fwd): go_amax / in_amax may each be NULL */

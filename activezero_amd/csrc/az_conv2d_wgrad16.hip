@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "az_roll_common.h"
+#include "az_launch_math.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -455,43 +456,12 @@ int az_conv2d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine
     a.B = B; a.H = H; a.W = W; a.CM = cm; a.CN = cn; a.cs_c = cs_c; a.cs_f = cs_f;
     a.nwchunk = (W + V16_POS - 1) / V16_POS;
     const int ntiles = (cm / 32) * (cn / 32);
-    const int slots = 256 * 3 / ntiles;  // resident workgroups per tile at three per CU
-    // row segments (even row counts): enough columns to fill the slots, long enough to amortise the window prologue
-    int best_seg = 1, best_w = 1;
-    double best = -1.0;
-    for (int nseg = 1; nseg <= 16; ++nseg) {
-        int rows = (H + nseg - 1) / nseg;
-        rows += rows & 1;
-        const int segs = (H + rows - 1) / rows;
-        const long long cols = (long long)B * a.nwchunk * segs;
-        const int w = (int)(cols < slots ? cols : slots);
-        const long long per = (cols + w - 1) / w;
-        const double balance = (double)cols / (double)(per * w);
-        const double occ = (double)w / (double)slots;
-        const double amort = (double)rows / (double)(rows + 4);
-        const double score = balance * (0.5 + 0.5 * occ) * amort;
-        if (score > best) { best = score; best_seg = segs; best_w = w; a.seg_rows = rows; }
-    }
-    a.nrseg = best_seg;
-    a.ncols = (long long)B * a.nwchunk * a.nrseg;
-    a.wgs = best_w;
-    if (coarse_amax && fine_amax && cm == 64 && cn == 64) {
-        // one 64 x 64 tile per workgroup of eight waves, one workgroup per CU
-        int best_seg2 = 1, best_w2 = 1;
-        double best2 = -1.0;
-        for (int nseg = 1; nseg <= 16; ++nseg) {
-            int rows = (H + nseg - 1) / nseg;
-            rows += rows & 1;
-            const int segs = (H + rows - 1) / rows;
-            const long long cols = (long long)B * a.nwchunk * segs;
-            const int w = (int)(cols < 256 ? cols : 256);
-            const long long per = (cols + w - 1) / w;
-            const double score = ((double)cols / (double)(per * w)) * (0.5 + 0.5 * (double)w / 256.0) * ((double)rows / (double)(rows + 4));
-            if (score > best2) { best2 = score; best_seg2 = segs; best_w2 = w; a.seg_rows = rows; }
-        }
-        a.nrseg = best_seg2;
-        a.ncols = (long long)B * a.nwchunk * a.nrseg;
-        a.wgs = best_w2;
+    // row segments and workgroups per tile: az_launch_math.h az_c2w16_plan (768 resident workgroups at three per CU over the
+    // tiles; the f16x3 64 x 64 layers: one 64 x 64 tile per workgroup of eight waves, one workgroup per CU)
+    const bool w64 = coarse_amax && fine_amax && cm == 64 && cn == 64;
+    const AzC2w16Plan p = az_c2w16_plan(B, H, W, w64 ? 256 : 256 * 3 / ntiles);
+    a.seg_rows = p.seg_rows; a.nrseg = p.nrseg; a.ncols = p.ncols; a.wgs = p.wgs;
+    if (w64) {
         hipLaunchKernelGGL(conv2d_wgrad_w64_kernel, dim3((unsigned)a.wgs), dim3(512), 0, s, a);
         return az_launch_status();
     }

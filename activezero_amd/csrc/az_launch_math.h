@@ -123,6 +123,72 @@ inline int az_wgrad16_workgroups(long long ncols, int slots, int ntiles, int cap
     return best;
 }
 
+// az_conv2d_wgrad16.hip (3x3 d1 2-D weight gradient, 32 / 64 channels): a column of work = (image, 16-position chunk, row
+// segment); `slots` = workgroups resident per (co, ci) tile (768 / ntiles at three per CU; 256 for the one-tile-per-workgroup
+// 64 x 64 kernel).  Row segments have EVEN row counts (a step multiplies a pair of dy rows): of the up to 16 splits the one
+// with the best (column balance) x (occupancy) x (rows per window prologue).  Postconditions: seg_rows even,
+// nrseg * seg_rows >= H, (nrseg - 1) * seg_rows < H, ncols = B * ceil(W / 16) * nrseg, 1 <= wgs <= min(slots, ncols).
+struct AzC2w16Plan { int seg_rows, nrseg, wgs; long long ncols; };
+inline AzC2w16Plan az_c2w16_plan(int B, int H, int W, int slots) {
+    const int nwchunk = (W + 15) / 16;
+    AzC2w16Plan p{};
+    p.nrseg = 1; p.wgs = 1;
+    double best = -1.0;
+    for (int nseg = 1; nseg <= 16; ++nseg) {
+        int rows = (H + nseg - 1) / nseg;
+        rows += rows & 1;
+        const int segs = (H + rows - 1) / rows;
+        const long long cols = (long long)B * nwchunk * segs;
+        const int w = (int)(cols < slots ? cols : slots);
+        const long long per = (cols + w - 1) / w;
+        const double balance = (double)cols / (double)(per * w);
+        const double occ = (double)w / (double)slots;
+        const double amort = (double)rows / (double)(rows + 4);
+        const double score = balance * (0.5 + 0.5 * occ) * amort;
+        if (score > best) { best = score; p.nrseg = segs; p.wgs = w; p.seg_rows = rows; }
+    }
+    p.ncols = (long long)B * nwchunk * p.nrseg;
+    return p;
+}
+
+// az_conv2d_wgrad.hip (the generic 2-D weight gradient, MT x NT waves per workgroup): static work lists -- block w of a
+// (co, ci) combo takes items w, w + blocks_per_combo, ... of the nitems = B * ceil(W / 16) * nhseg (image, row segment,
+// chunk) items; the kernel ends with its most loaded block, so (row segments, blocks per combo) are picked with the item count
+// a near multiple of the block count while ncombo * blocks * MT * NT stays close to the resident waves.  ring_rows =
+// DIL * (KH - 1) + 1 rows of x are staged before an item's first output row.  Postconditions: nhseg * hseg_rows >= H,
+// (nhseg - 1) * hseg_rows < H, blocks_per_combo >= 8 and a multiple of 8 (blocks b and b + 8 share an XCD).
+struct AzC2wPlan { int blocks_per_combo, hseg_rows, nhseg; long long nitems; };
+inline AzC2wPlan az_c2w_plan(int B, int H, int W, int mt, int nt, int ncombo, int ring_rows) {
+    const int nwchunk = (W + 15) / 16;
+    const int slots = 256 * 8 / (mt * nt);  // resident workgroups at 2 waves/SIMD
+    const int wq = (slots / ncombo) & ~7;
+    const int wmax = wq > 8 ? wq : 8;
+    const int wmin = wmax / 2 > 8 ? wmax / 2 : 8;
+    const long long base_items = (long long)B * nwchunk;
+    double best = -1.0;
+    int best_w = 8, best_rows = H;
+    for (int nseg = 1; nseg <= (H < 32 ? H : 32); ++nseg) {
+        const int rows = (H + nseg - 1) / nseg;
+        const int segs = (H + rows - 1) / rows;
+        const long long items = base_items * segs;
+        for (int w = wmax; w >= wmin; w -= 8) {
+            const long long per = (items + w - 1) / w;
+            const double balance = (double)items / (double)(per * w);
+            const double occ = (double)w / (double)wmax;
+            const double amort = (double)rows / (double)(rows + ring_rows - 1 + 2);  // ring prologue per item
+            const double score = balance * (0.5 + 0.5 * occ) * amort;
+            if (score > best) { best = score; best_w = w; best_rows = rows; }
+        }
+    }
+    AzC2wPlan p{};
+    p.blocks_per_combo = best_w;
+    p.hseg_rows = best_rows;
+    p.nhseg = (H + best_rows - 1) / best_rows;
+    p.nitems = base_items * p.nhseg;
+    if (p.nitems < p.blocks_per_combo) p.blocks_per_combo = (int)((p.nitems + 7) & ~7LL);
+    return p;
+}
+
 // az_conv3d_wgrad16s2.hip (stride-2 weight gradient): a step stages 3 planes x 8 new fine rows x 17 positions x 8 float4
 // pieces.  Piece f -> plane pk, row j, position pp (fine x = 2 cw0 - 1 + pp) and the LDS row of the position inside a
 // staged row: the ODD fine positions (pp even) are rows 0..8, the EVEN ones rows 9..16, so that tap kw of coarse position x

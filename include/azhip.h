@@ -442,6 +442,17 @@ long long az_conv2d_wgrad_workspace(int cm, int cn, int kh, int kw);
 int az_conv2d_wgrad(float *grad_w, float *workspace, long long workspace_bytes, const float *grad_out,
                     const float *in, int B, int H, int W, int cm, int cn, int cm_real, int cn_real,
                     int go_cstride, int in_cstride, int kh, int kw, int dilation, void *stream);
+/* Which kernel az_conv2d_wgrad (f16 = 0) / az_conv2d_wgrad_f16 (f16 = 1) launches for a shape under the current switches, and
+ * that kernel's launch plan, computed by the functions the launch itself calls.  plan[0] = AZ_C2W_KERNEL_*;
+ * R16_AR0 / R16_AR1 / W64 (az_conv2d_wgrad16.hip; a column = (image, 16-position chunk, row segment)): plan[1] = rows per row
+ * segment (even), [2] = row segments, [3] = columns per (co, ci) tile, [4] = workgroups per tile, [5] = resident slots per tile;
+ * GENERIC (az_conv2d_wgrad.hip, MT x NT waves of 32 x 32 channels): plan[1] = MT, [2] = NT, [3] = blocks per (co, ci) combo,
+ * [4] = rows per row segment, [5] = row segments, [6] = work items per combo, [7] = launches (3x5: one per kernel row). */
+#define AZ_C2W_KERNEL_R16_AR0 0
+#define AZ_C2W_KERNEL_R16_AR1 1
+#define AZ_C2W_KERNEL_W64 2
+#define AZ_C2W_KERNEL_GENERIC 3
+int az_conv2d_wgrad_plan(long long *plan /* [8] */, int f16, int B, int H, int W, int cm, int cn, int kh, int kw, int dilation);
 /* az_conv2d_fwd without epilogue operands that also emits the BatchNorm partials of its (raw) output -- per channel
  * and 8x16 patch (sum, M2 about the patch mean), layout [groups][cout][tiles][2] + counts [groups][tiles] with
  * tiles = az_conv2d_stats_tiles() -- which az_bn2d_fwd accepts in place of its own statistics pass over the tensor

@@ -19,7 +19,14 @@ Checks per output, all element-wise:
       products.  sqrt(K sum (p q)^2) >= S, so at small K (c) is about as loose as (b); for zero-mean operands it grows like
       K where S sqrt(K / 32) grows like K^1.5.  On a V0-sized weight gradient (K = 1.6e6) one 16-position column counted
       twice lands at 6 times (b)'s bound and at 600 times (c)'s (measured by tests/test_gpu_conv3d_s1.py).
+
+Every function takes a geometry `geom`; None is the 3-D family above.  A Geom2d(kh, kw, dil, stride) is a 2-D convolution with
+"same" padding dil (k - 1) / 2 (3x3 d1, 3x3 d2, 1x1, 3x5; stride 2 only for the 3x3 pad-1 layer of the patch route), operands
+x: [B,cin,H,W], w: [cout,cin,kh,kw], dy: [B,cout,Ho,Wo], with K = kh kw cin (fwd), kh kw cout (dgrad), B Ho Wo (wgrad)
+(tests/test_gpu_conv2d_fp64.py).
 """
+import collections
+import functools
 import math
 import struct
 
@@ -35,6 +42,26 @@ ARITHS = ("f16x3", "bf16x6", "fp32")
 # and behind each switch of its rows in tests/test_gpu_switches.py.  The maxima sit at the smallest K (a weight gradient of
 # 9 positions), where the few roundings of the chained MFMAs, the flush and the unpack are not averaged out -- but for fp32 (c):
 # a forward of K = 1728 on v_mfma_f32_32x32x2_f32, which rounds every 2 products instead of every 16 or 32.
+#
+# The 2-D family (tests/test_gpu_conv2d_fp64.py) uses the same constants; largest err / bound of checks (b) / (c) measured on an
+# MI355X per arithmetic, kind and route (the maxima again sit at the smallest K: the 1 x 1 image and the 1x1 layers):
+#                                              bf16x6 (b)  (c)     f16x3 (b)  (c)
+#   fwd    roll NT 2 (plain / stats / epi)        0.13   0.23         0.13   0.25
+#   fwd    roll NT 4 | roll64 (f16x3)             0.16   0.25         0.28   0.48   (roll64 + stats, 32 -> 64, (134, 9, 50), groups 2)
+#   fwd    generic, all NW and geometries         0.16   0.24         0.20   0.29   (1x1, 64 -> 128, (3, 5, 47))
+#   dgrad  roll NT 2 (+ residual)                 0.13   0.20         0.20   0.26
+#   dgrad  roll NT 4 | roll64 (+ residual)        0.16   0.25         0.27   0.45   (64 -> 32, (131, 9, 50) and (13, 64, 80))
+#   dgrad  generic, all NW and geometries         0.29   0.40         0.33   0.42   (1x1, 128 -> 32, (2, 13, 22))
+#   wgrad  r16 AR 0 | AR 1                        0.30   0.39         0.41   0.51   ((1, 1, 1) image)
+#   wgrad  w64                                      --     --         0.38   0.47   ((1, 1, 1) image)
+#   wgrad  generic 3x3 d1 / 3x3 d2 / 3x5          0.07   0.19         0.11   0.29
+#   wgrad  generic 1x1                            0.29   0.37         0.42   0.52   (128 -> 32, (1, 1, 1) image)
+#   patch route (bf16x6 only)   fwd               0.31   0.36                        (3 -> 32, (2, 13, 22): K = 27)
+#                               dgrad             0.15   0.11
+#                               wgrad             0.20   0.27                        (6 -> 32, (1, 1, 1) image)
+# The walking and segmented cases (batch segments of 3 images, 770 columns for 768 / 384 / 256 / 192 workgroups, 3 to 8 row
+# segments, 770 items for 200 blocks) stay below 0.13 in (b) and 0.25 in (c) but for roll64 above; check (a) peaks at 0.41
+# (f16x3 r16 AR 1, (1, 1, 1) image).
 C = {
     "f16x3": 2.0,   # measured max 1.17 (wide weight gradient, 64 -> 32, (1, 1, 3, 3))
     "bf16x6": 3.0,  # measured max 1.51 (r16 AR 0 weight gradient, 64 -> 64, (1, 1, 3, 3))
@@ -47,10 +74,33 @@ C2 = {
 }
 
 
+class Geom2d(collections.namedtuple("Geom2d", "kh kw dil stride in_hw", defaults=(1, 1, None))):
+    """a 2-D geometry; in_hw: (H, W) of x where the stride leaves it open (the input gradient of a stride-2 layer)"""
+
+    @property
+    def pad(self):
+        return (self.dil * (self.kh - 1) // 2, self.dil * (self.kw - 1) // 2)
+
+
 # ---- fp64 operators ---------------------------------------------------------------------------------------------------
-def op(kind, p, q):
+def _op2d(kind, p, q, g):
+    st, dl = g.stride, g.dil
+    if kind == "fwd":
+        return F.conv2d(p, q, stride=st, padding=g.pad, dilation=dl)
+    if kind == "dgrad":
+        opad = (0, 0)
+        if st > 1:  # the rows / columns of x a stride leaves without an output position of their own
+            opad = tuple(n - ((m - 1) * st - 2 * pd + dl * (k - 1) + 1) for n, m, pd, k in
+                         zip(g.in_hw, p.shape[2:], g.pad, (g.kh, g.kw)))
+        return F.conv_transpose2d(p, q, stride=st, padding=g.pad, dilation=dl, output_padding=opad)
+    return torch.nn.grad.conv2d_weight(p, (q.shape[1], p.shape[1], g.kh, g.kw), q, stride=st, padding=g.pad, dilation=dl)
+
+
+def op(kind, p, q, geom=None):
     """the fp64 operation (torch's convolutions; any device that has them)"""
     p, q = p.double(), q.double()
+    if geom is not None:
+        return _op2d(kind, p, q, geom)
     if kind == "fwd":
         return F.conv3d(p, q, padding=1)
     if kind == "dgrad":
@@ -64,10 +114,40 @@ def _neighbourhoods(xp, b, d, h, w):
     return torch.stack(taps, dim=2).reshape(h * w, -1)
 
 
-def op_gemm(kind, p, q):
+def _op_gemm2d(kind, p, q, g):
+    """stride-1 geometries: one matrix product per image over its [H W, kh kw C] neighbourhood rows"""
+    assert g.stride == 1
+    if kind == "dgrad":  # conv_transpose2d(dy, w) = conv2d(dy, w with taps flipped and channels swapped)
+        kind, q = "fwd", q.transpose(0, 1).flip(2, 3)
+    b, c, h, w = p.shape
+    ph, pw = g.pad
+    taps = g.kh * g.kw
+    xp = F.pad(p.permute(0, 2, 3, 1), (0, 0, pw, pw, ph, ph))  # [B, H+2ph, W+2pw, C]
+
+    def rows(bi):
+        t = [xp[bi, i * g.dil:i * g.dil + h, j * g.dil:j * g.dil + w, :] for i in range(g.kh) for j in range(g.kw)]
+        return torch.stack(t, dim=2).reshape(h * w, taps * c)
+
+    if kind == "fwd":
+        cout = q.shape[0]
+        wm = q.permute(2, 3, 1, 0).reshape(taps * c, cout)
+        y = torch.empty(b, h * w, cout, dtype=torch.float64, device=p.device)
+        for bi in range(b):
+            y[bi] = rows(bi) @ wm
+        return y.reshape(b, h, w, cout).permute(0, 3, 1, 2)
+    cout = q.shape[1]
+    acc = torch.zeros(cout, taps * c, dtype=torch.float64, device=p.device)
+    for bi in range(b):
+        acc += q[bi].reshape(cout, h * w) @ rows(bi)
+    return acc.reshape(cout, taps, c).permute(0, 2, 1).reshape(cout, c, g.kh, g.kw)
+
+
+def op_gemm(kind, p, q, geom=None):
     """the same values as op(), as unfold + float64 matrix products over depth planes: no fp64 convolution of a vendor
     library is involved (the references of the large shapes are computed this way on the GPU)"""
     p, q = p.double(), q.double()
+    if geom is not None:
+        return _op_gemm2d(kind, p, q, geom)
     if kind == "dgrad":  # conv_transpose3d(dy, w) = conv3d(dy, w with taps flipped and channels swapped)
         kind, q = "fwd", q.transpose(0, 1).flip(2, 3, 4)
     b, c, d, h, w = p.shape
@@ -88,19 +168,21 @@ def op_gemm(kind, p, q):
     return g.reshape(cout, 27, c).permute(0, 2, 1).reshape(cout, c, 3, 3, 3)
 
 
-def products(kind, p, q):
+def products(kind, p, q, geom=None):
     """K: products per output"""
+    if geom is not None:
+        return q.shape[0] * q.shape[2] * q.shape[3] if kind == "wgrad" else geom.kh * geom.kw * p.shape[1]
     if kind == "wgrad":
         b, _, d, h, w = p.shape
         return b * d * h * w
     return 27 * p.shape[1]
 
 
-def exact(kind, p, q, gemm=False):
+def exact(kind, p, q, gemm=False, geom=None):
     """fp64 result and the per-output magnitude sums: S = sum |p_k q_k|, Q2 = sum (p_k q_k)^2, sum_q = sum |q_k| and
     sum_p = sum |p_k| (the sums the f16x3 amax term multiplies with the amax of p and of q).  (Padding stays zero in the
     ones.)"""
-    f = op_gemm if gemm else op
+    f = functools.partial(op_gemm if gemm else op, geom=geom)
     p, q = p.double(), q.double()
     ap, aq = p.abs(), q.abs()
     return {"y": f(kind, p, q), "S": f(kind, ap, aq), "Q2": f(kind, p * p, q * q), "sum_q": f(kind, torch.ones_like(p), aq),
@@ -142,14 +224,16 @@ def split_parts(t, arith, amax=None):
     return [t.double()]
 
 
-def split_reference(kind, p, q, arith, parts_p=None, parts_q=None, gemm=False):
+def split_reference(kind, p, q, arith, parts_p=None, parts_q=None, gemm=False, geom=None):
     """fp64 value of exactly the products the arithmetic forms:
     f16x3  -- hi*hi + hi*lo + lo*hi (lo*lo dropped);
     bf16x6 -- the six products of az_conv3d_wgrad16.hip's chain: lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi (mid*lo,
               lo*mid, lo*lo dropped);
     fp32   -- the fp32 operands' exact bilinear form.
-    parts_p / parts_q: parts already split (a pre-split tensor decoded from its bits) in place of split_parts()"""
-    f = op_gemm if gemm else op
+    parts_p / parts_q: parts already split (a pre-split tensor decoded from its bits) in place of split_parts().
+    The 2-D kernels form the same sets: az_mfma6 / az_mfma6_now / r16_step of az_common.h and az_roll_common.h multiply hi*hi,
+    hi*mid, mid*hi, mid*mid, hi*lo, lo*hi; az_mfma3_* / r16_step3 / r16_chain9 hi*hi, hi*lo, lo*hi."""
+    f = functools.partial(op_gemm if gemm else op, geom=geom)
     pp = parts_p if parts_p is not None else split_parts(p, arith)
     qq = parts_q if parts_q is not None else split_parts(q, arith)
     if arith == "f16x3":
@@ -160,16 +244,40 @@ def split_reference(kind, p, q, arith, parts_p=None, parts_q=None, gemm=False):
 
 
 # ---- the two checks -----------------------------------------------------------------------------------------------------
-def rounding_count(arith, K):
+def rounding_count(arith, K, blocks=None):
     """fp32 roundings an output may see in the worst case: every MFMA rounds the accumulator it is chained into (f16x3: 3
     per 16-deep block of v_mfma_*_f16, bf16x6: 6 per 16-deep block, fp32: v_mfma_f32_32x32x2_f32 rounds each of its 2
-    products and adds), plus one fp32 add per block for block sums and partial-sum flushes, plus 3 for the epilogue"""
-    blocks = math.ceil(K / 16)
+    products and adds), plus one fp32 add per block for block sums and partial-sum flushes, plus 3 for the epilogue.
+
+    The 2-D kernels, read against this count:
+      * az_conv2d.hip (forward / input gradient): per tap and 16-channel chunk one 16-deep block of 3 / 6
+        v_mfma_f32_32x32x16 chained from ZERO in a block temporary (az_mfma6_step / _now, az_mfma3_*) and one fp32 add of the
+        temporary into the accumulator -- its acc[0..3] are four M tiles, not partial sums of one output.  kh kw cin / 16
+        blocks = ceil(K / 16) exactly (cin % 16 == 0; the patch route's K = 9 cin is padded with zero products to Kp = 32 / 64:
+        ceil(27 / 16) = 32 / 16, ceil(54 / 16) = 64 / 16), so chain + blocks covers it.
+      * az_conv2d_roll.hip: 32-deep blocks (r16_step / r16_step3: 6 / 3 v_mfma_f32_16x16x32 from zero + one add; roll64's
+        r16_chain9: nine MFMAs over three 32-deep blocks + one add): half as many chain roundings as counted, and at most as
+        many adds.
+      * the weight gradients: their K blocks are not K / 16 consecutive positions but (image, row or row pair, 16-position
+        chunk) pieces -- az_conv2d_wgrad.hip one 16-deep block per output row and chunk, az_conv2d_wgrad16.hip one 32-deep
+        block per PAIR of rows and chunk -- so a ragged W (W = 47: three chunks, the last 15 / 16 full) gives an output up to
+        B H ceil(W / 16) blocks with non-zero products where ceil(B H W / 16) would count fewer.  `blocks` carries that number
+        (wgrad_blocks_2d); every block is 3 / 6 MFMAs chained into the running accumulator (no temporary there).  The flushes:
+        one atomicAdd per workgroup and output, at most one workgroup per column = (image, chunk, row segment) <= B ceil(W / 16)
+        H, within the `+ blocks` adds; the unpack copies."""
+    blocks = math.ceil(K / 16) if blocks is None else max(blocks, math.ceil(K / 16))
     chain = {"f16x3": 3 * blocks, "bf16x6": 6 * blocks, "fp32": 2 * K}[arith]
     return chain + blocks + 3
 
 
-def bound_a(arith, K, ex, amax_p, amax_q):
+def wgrad_blocks_2d(dy):
+    """K blocks with non-zero products an output of a 2-D weight gradient may see (rounding_count): B H ceil(W / 16) for
+    a gradient dy [B, C, H, W]"""
+    b, _, h, w = dy.shape
+    return b * h * ((w + 15) // 16)
+
+
+def bound_a(arith, K, ex, amax_p, amax_q, blocks=None):
     """the worst-case bound (check a).  f16x3: include/azhip.h "CONTRACT of a caller-supplied amax",
         [3 * 2^-22 + n * 2^-24] * S + 2^-38 * (A_p * sum |q| + A_q * sum |p|)
     (3 * 2^-22: the two-part split of both operands and the dropped lo*lo; 2^-38 A: the fp16 subnormal spacing of `lo`),
@@ -178,7 +286,7 @@ def bound_a(arith, K, ex, amax_p, amax_q):
     bf16x6: 5 * 2^-24 * S for the split (hi + mid + lo = x up to 2^-24 |x| per operand, the dropped mid*lo and lo*mid up to
     2^-24 |x y| each) + n * 2^-24 * S.  fp32: n * 2^-24 * S (the operands are exact)."""
     rep = {"f16x3": 12.0, "bf16x6": 5.0, "fp32": 0.0}[arith]
-    lim = (rep + rounding_count(arith, K)) * U * ex["S"]
+    lim = (rep + rounding_count(arith, K, blocks)) * U * ex["S"]
     if arith == "f16x3":
         lim = lim + 2.0 ** -38 * (amax_p * ex["sum_q"] + amax_q * ex["sum_p"])
     return lim
@@ -202,18 +310,32 @@ def _ratio(err, lim):
     return float((err[pos] / lim[pos]).max()) if bool(pos.any()) else 0.0
 
 
-def check(got, arith, K, ex, sref, amax_p=0.0, amax_q=0.0, addend=None):
+def check(got, arith, K, ex, sref, amax_p=0.0, amax_q=0.0, addend=None, blocks=None, epilogue=None):
     """the three checks for every output; returns (ratio a, ratio b, ratio c), the largest err / bound of each (<= 1
     passes).
     addend: a tensor the kernel added in fp32 after the sum (the residual of the gradient hand-over): it is added to both
-    references, and one more rounding of the total is allowed"""
+    references, and one more rounding of the total is allowed
+    blocks: rounding_count's block count where ceil(K / 16) is not it (2-D weight gradients)
+    epilogue: (scale [C], shift [C], res or None, relu) of the fused relu?(conv * scale + shift + res) on dim 1: applied in
+    fp64 to both references; the three bounds scale with |scale|, and 3 2^-24 (|conv scale| + |shift| + |res|) is allowed
+    for its three roundings (ReLU does not increase a difference)"""
     got = got.double().to(ex["y"].device)
     y, sr = ex["y"], sref
-    la, lb, lc = bound_a(arith, K, ex, amax_p, amax_q), bound_b(arith, K, ex), bound_c(arith, K, ex)
+    la, lb, lc = bound_a(arith, K, ex, amax_p, amax_q, blocks), bound_b(arith, K, ex), bound_c(arith, K, ex)
     if addend is not None:
         a = addend.double().to(y.device)
         y, sr = y + a, sr + a
         la, lb, lc = la + U * y.abs(), lb + U * y.abs(), lc + U * y.abs()
+    if epilogue is not None:
+        scale, shift, res, relu = epilogue
+        bc = (lambda t: t.double().to(y.device).reshape(1, -1, *([1] * (y.dim() - 2))))
+        sc, sh = bc(scale), bc(shift)
+        r = res.double().to(y.device) if res is not None else torch.zeros_like(y)
+        extra = 3.0 * U * ((y * sc).abs() + sh.abs() + r.abs())
+        la, lb, lc = la * sc.abs() + extra, lb * sc.abs() + extra, lc * sc.abs() + extra
+        y, sr = y * sc + sh + r, sr * sc + sh + r
+        if relu:
+            y, sr = y.clamp_min(0.0), sr.clamp_min(0.0)
     if not bool(torch.isfinite(got).all()):
         return float("inf"), float("inf"), float("inf")
     eb = (got - sr).abs()

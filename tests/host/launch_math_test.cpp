@@ -205,6 +205,59 @@ int main() {
             for (long long c = 0; c < ncols; ++c) CHECK(seen_col[(size_t)c], "column %lld never walked", c);
         }
     }
+    // 8. plans of the 2-D weight gradients (az_conv2d_wgrad16.hip, az_conv2d_wgrad.hip): row segments tile [0, H), the
+    //    persistent workgroups / static work lists visit every column / item exactly once
+    {
+        const int Bs[] = {1, 2, 3, 8, 13, 131}, Hs[] = {1, 2, 3, 5, 9, 13, 24, 37, 47, 64, 136, 271},
+                  Ws[] = {1, 15, 16, 17, 22, 47, 53, 150, 240, 400, 12320};
+        const int slot_counts[] = {768, 384, 192, 256};
+        for (int B : Bs) for (int H : Hs) for (int W : Ws) {
+            const int nwchunk = (W + 15) / 16;
+            for (int slots : slot_counts) {
+                const AzC2w16Plan p = az_c2w16_plan(B, H, W, slots);
+                CHECK(p.seg_rows >= 2 && p.seg_rows % 2 == 0, "r16 B%d H%d W%d slots %d: seg_rows %d", B, H, W, slots, p.seg_rows);
+                CHECK(p.nrseg >= 1 && p.nrseg <= 16 && (long long)p.nrseg * p.seg_rows >= H && (long long)(p.nrseg - 1) * p.seg_rows < H,
+                      "r16 B%d H%d W%d slots %d: %d segments of %d rows", B, H, W, slots, p.nrseg, p.seg_rows);
+                CHECK(p.ncols == (long long)B * nwchunk * p.nrseg, "r16 ncols %lld", p.ncols);
+                CHECK(p.wgs >= 1 && p.wgs <= slots && p.wgs <= p.ncols, "r16 B%d H%d W%d slots %d: wgs %d of %lld columns", B, H, W, slots, p.wgs, p.ncols);
+                if (p.ncols > 20000) continue;
+                // the kernels' walk: workgroup wg takes columns wg, wg + wgs, ...; a column decodes to a non-empty row range
+                std::vector<char> seen((size_t)p.ncols, 0);
+                for (int wg = 0; wg < p.wgs; ++wg)
+                    for (long long col = wg; col < p.ncols; col += p.wgs) {
+                        CHECK(!seen[(size_t)col], "r16 column %lld twice", col);
+                        seen[(size_t)col] = 1;
+                        long long r = col;
+                        const int rs = (int)(r % p.nrseg); r /= p.nrseg;
+                        const int wc = (int)(r % nwchunk), b = (int)(r / nwchunk);
+                        const int h0 = rs * p.seg_rows, h1 = h0 + p.seg_rows < H ? h0 + p.seg_rows : H;
+                        CHECK(b >= 0 && b < B && wc < nwchunk && h0 % 2 == 0 && h0 < h1, "r16 column %lld -> b %d chunk %d rows [%d, %d)", col, b, wc, h0, h1);
+                    }
+                for (long long c = 0; c < p.ncols; ++c) CHECK(seen[(size_t)c], "r16 column %lld never walked", c);
+            }
+            for (int mt = 1; mt <= 2; ++mt) for (int nt = 1; nt <= 2; ++nt)
+                for (int cm = 32 * mt; cm <= 192; cm += 64 * mt) for (int cn = 32 * nt; cn <= 192; cn += 64 * nt)
+                    for (int ring = 1; ring <= 5; ring += 2) {
+                        const int ncombo = (cm / (32 * mt)) * (cn / (32 * nt));
+                        const AzC2wPlan p = az_c2w_plan(B, H, W, mt, nt, ncombo, ring);
+                        CHECK(p.hseg_rows >= 1 && p.nhseg >= 1 && (long long)p.nhseg * p.hseg_rows >= H && (long long)(p.nhseg - 1) * p.hseg_rows < H,
+                              "w2 B%d H%d W%d %dx%d: %d segments of %d rows", B, H, W, mt, nt, p.nhseg, p.hseg_rows);
+                        CHECK(p.nitems == (long long)B * nwchunk * p.nhseg, "w2 nitems %lld", p.nitems);
+                        CHECK(p.blocks_per_combo >= 8 && p.blocks_per_combo % 8 == 0, "w2 blocks per combo %d", p.blocks_per_combo);
+                        CHECK((long long)p.blocks_per_combo * ncombo <= 2048 / (mt * nt) + 8LL * ncombo, "w2 grid %d x %d", p.blocks_per_combo, ncombo);
+                        // the kernel's block -> (combo, list index) map: every (combo, index) once, the lists cover the items
+                        const int nblk = p.blocks_per_combo * ncombo;
+                        std::vector<char> taken((size_t)nblk, 0);
+                        for (int bid = 0; bid < nblk; ++bid) {
+                            const int grp = bid / (8 * ncombo), rem = bid % (8 * ncombo);
+                            const int combo = rem >> 3, widx = grp * 8 + (rem & 7);
+                            CHECK(combo < ncombo && widx < p.blocks_per_combo, "w2 block %d -> combo %d list %d", bid, combo, widx);
+                            const int id = combo * p.blocks_per_combo + widx;
+                            if (id >= 0 && id < nblk) { CHECK(!taken[(size_t)id], "w2 list %d twice", id); taken[(size_t)id] = 1; }
+                        }
+                    }
+        }
+    }
     std::printf("launch math: %d failures\n", fails);
     return fails ? 1 : 0;
 }

@@ -148,3 +148,234 @@ def test_split_parts_are_the_documented_splits():
     parts = R.split_parts(t, "bf16x6")
     assert bool(((sum(parts) - t.double()).abs() <= 2.0 ** -24 * t.double().abs()).all())
     assert R.split_parts(t, "fp32")[0].equal(t.double())
+
+
+# ---- the 2-D family (tests/test_gpu_conv2d_fp64.py) ----------------------------------------------------------------------------
+G33, G33D2, G11, G35 = R.Geom2d(3, 3, 1), R.Geom2d(3, 3, 2), R.Geom2d(1, 1, 1), R.Geom2d(3, 5, 1)
+SHAPES2D = [(2, 13, 22), (1, 16, 32), (3, 5, 47), (2, 37, 53), (1, 1, 1)]  # the small shapes of the GPU file
+GEOMS2D = [(G33, SHAPES2D), (G33D2, [(2, 13, 22), (1, 1, 1)]), (G11, [(3, 5, 47), (1, 1, 1)]), (G35, [(2, 13, 22), (1, 1, 1)])]
+SEG_LEN = 3  # images per batch segment of the emulated walk (the GPU file's walking cases have seg_len 3)
+
+
+def operands2d(kind, shape, geom, cin=32, cout=32, seed=7600):
+    b, h, w = shape
+    x = seeded((b, cin, h, w), seed)
+    wt = seeded((cout, cin, geom.kh, geom.kw), seed + 1, -0.2, 0.2)
+    dy = seeded((b, cout, h, w), seed + 2) * 1e-3
+    return {"fwd": (x, wt), "dgrad": (dy, wt), "wgrad": (x, dy)}[kind]
+
+
+def seam_row(h):
+    """first row of the second row segment of a weight gradient split into two even-length segments (az_c2w16_plan)"""
+    rows = (h + 1) // 2
+    return rows + (rows & 1)
+
+
+def halo_row(h):
+    """an output row whose kh = 0 tap lies in the halo of its 8-row patch (the first row of the second patch row, else row 1)"""
+    return 8 if h > 8 else 1
+
+
+def unfold2d(t, geom, mutant=None):
+    """[B,C,H,W] (fp64) -> [B*H*W, kh*kw*C] neighbourhoods (tap-major).
+    w_edge: the taps right of the last image column read that column instead of the zero padding;
+    halo_prev: the row above output row halo_row(H) of every image but the first is read from the previous image of the walk"""
+    b, c, h, w = t.shape
+    ph, pw = geom.pad
+    xp = F.pad(t.permute(0, 2, 3, 1), (0, 0, pw, pw, ph, ph))
+    if mutant == "w_edge" and pw:
+        xp[:, :, w + pw:, :] = xp[:, :, w + pw - 1:w + pw, :]
+    out = []
+    for bi in range(b):
+        img = xp[bi]
+        taps = []
+        for i in range(geom.kh):
+            for j in range(geom.kw):
+                v = img[i * geom.dil:i * geom.dil + h, j * geom.dil:j * geom.dil + w, :].clone()
+                if mutant == "halo_prev" and bi > 0 and i == 0 and ph:
+                    r = halo_row(h)
+                    v[r] = xp[bi - 1][i * geom.dil + r, j * geom.dil:j * geom.dil + w, :]
+                taps.append(v)
+        out.append(torch.stack(taps, dim=2).reshape(h * w, -1))
+    return torch.cat(out)
+
+
+def position_weights2d(shape, mutant):
+    """per position (b, h, w order) how often the weight-gradient kernels' K blocks count it"""
+    b, h, w = shape
+    m = torch.ones(b, h, w, dtype=torch.float64)
+    if mutant == "seam_row_twice":    # the first row of the second row segment also counted by the first segment
+        m[:, seam_row(h), :] = 2.0
+    if mutant == "seam_row_dropped":  # ... or by neither
+        m[:, seam_row(h), :] = 0.0
+    if mutant == "column_twice":      # one (image, 16-position chunk) column walked by two workgroups
+        m[b - 1, :, 16 * ((w - 1) // 16):] = 2.0
+    return m.reshape(-1)
+
+
+def emulate2d(kind, p, q, arith, geom, mutant=None):
+    """the 2-D kernels' result in the emulated arithmetic (NCHW / weight layout, fp32): exact sums of the defined products
+    per 32-deep K block, fp32 accumulation of the block sums"""
+    terms = list(TERMS[arith])
+    if mutant == "hilo_dropped":
+        terms.remove((0, 1))
+    pp, qq = R.split_parts(p, arith), R.split_parts(q, arith)
+    if mutant == "lo_scale":
+        pp[1] = pp[1] * 2.0
+    if kind == "dgrad":
+        qq = [t.transpose(0, 1).flip(2, 3) for t in qq]
+    b, _, h, w = p.shape
+    if kind in ("fwd", "dgrad"):
+        cout = qq[0].shape[0]
+        a = [unfold2d(t, geom, mutant) for t in pp]
+        bm = [t.permute(2, 3, 1, 0).reshape(-1, cout) for t in qq]
+    else:
+        cout = qq[0].shape[1]
+        pw = position_weights2d((b, h, w), mutant)
+        a = [(t.permute(1, 0, 2, 3).reshape(cout, -1) * pw) for t in qq]
+        bm = [unfold2d(t, geom, mutant) for t in pp]
+    K = a[0].shape[1]
+    acc = torch.zeros(a[0].shape[0], bm[0].shape[1], dtype=torch.float32)
+    for k0 in range(0, K, 32):
+        blk = sum(a[i][:, k0:k0 + 32] @ bm[j][k0:k0 + 32] for (i, j) in
+                  (terms if kind == "wgrad" else [(j, i) for (i, j) in terms]))
+        acc = acc + blk.float()
+    if kind == "wgrad":
+        cin = p.shape[1]
+        return acc.reshape(cout, geom.kh * geom.kw, cin).permute(0, 2, 1).reshape(cout, cin, geom.kh, geom.kw)
+    y = acc.reshape(b, h, w, cout).permute(0, 3, 1, 2).clone()
+    if mutant == "last_image_skipped":  # the last image of a ragged batch segment never multiplied: its output stays as
+        y[b - 1] = 0.0                  # the buffer was (zero here)
+    return y
+
+
+def ratios2d(kind, shape, arith, geom, mutant=None):
+    p, q = operands2d(kind, shape, geom)
+    got = emulate2d(kind, p, q, arith, geom, mutant)
+    ex = R.exact(kind, p, q, geom=geom)
+    sref = R.split_reference(kind, p, q, arith, geom=geom)
+    blocks = R.wgrad_blocks_2d(q) if kind == "wgrad" else None
+    return R.check(got, arith, R.products(kind, p, q, geom), ex, sref, R.amax_of(p), R.amax_of(q), blocks=blocks)
+
+
+_EMU2D = [(g, s) for (g, shapes) in GEOMS2D for s in shapes]
+
+
+@pytest.mark.parametrize("geom,shape", _EMU2D, ids=[f"{g.kh}x{g.kw}d{g.dil}-{s}" for (g, s) in _EMU2D])
+@pytest.mark.parametrize("kind", R.KINDS)
+@pytest.mark.parametrize("arith", ["f16x3", "bf16x6"])
+def test_emulated_2d_arithmetic_passes_the_checks(arith, kind, geom, shape, capsys):
+    r = ratios2d(kind, shape, arith, geom)
+    with capsys.disabled():
+        print(f"\nemulated 2-D {arith} {kind} {tuple(geom[:3])} {shape}: (a) {r[0]:.4f} (b) {r[1]:.4f} (c) {r[2]:.4f}")
+    assert max(r) <= 1.0, r
+
+
+_SEAM = [s for s in SHAPES2D if s[1] >= 3]                 # a second row segment exists
+_RAGGED = [s for s in SHAPES2D if s[0] % SEG_LEN]          # the last batch segment is shorter than SEG_LEN
+_HALO = [s for s in SHAPES2D if s[0] >= 2 and s[1] >= 2]   # a previous image and a row above
+_WIDE = [s for s in SHAPES2D if s != (1, 1, 1)]
+ARITHS2D = ("f16x3", "bf16x6")
+MUTANTS2D = [  # (mutant, kinds, geometry, shapes it applies to)
+    ("seam_row_twice", ("wgrad",), G33, _SEAM),
+    ("seam_row_dropped", ("wgrad",), G33, _SEAM),
+    ("column_twice", ("wgrad",), G33, SHAPES2D),
+    ("last_image_skipped", ("fwd",), G33, _RAGGED),
+    ("halo_prev", ("fwd", "dgrad"), G33, _HALO),
+    ("hilo_dropped", R.KINDS, G33, SHAPES2D),
+    ("lo_scale", R.KINDS, G33, SHAPES2D),
+    ("w_edge", R.KINDS, G33, SHAPES2D),
+    ("w_edge", R.KINDS, G35, [(2, 13, 22), (1, 1, 1)]),
+    ("w_edge", R.KINDS, G33D2, [(2, 13, 22), (1, 1, 1)]),
+    ("hilo_dropped", R.KINDS, G11, [(3, 5, 47), (1, 1, 1)]),
+]
+_CASES2D = [(m, a, k, g, s) for (m, kinds, g, shapes) in MUTANTS2D for a in ARITHS2D for k in kinds for s in shapes]
+
+
+@pytest.mark.parametrize("mutant,arith,kind,geom,shape", _CASES2D,
+                         ids=[f"{m}-{a}-{k}-{g.kh}x{g.kw}d{g.dil}-{s}" for (m, a, k, g, s) in _CASES2D])
+def test_2d_mutant_fails_a_check(mutant, arith, kind, geom, shape, capsys):
+    r = ratios2d(kind, shape, arith, geom, mutant)
+    with capsys.disabled():
+        print(f"\n2-D mutant {mutant} {arith} {kind} {shape}: (a) {r[0]:.3g} (b) {r[1]:.3g} (c) {r[2]:.3g}")
+    assert max(r) > 1.0, r
+
+
+# the patch route of firstconv.0: 3x3, stride 2, pad 1 on a 3- / 6-channel image as patches [.., Kp] x a 1x1 layer on Kp
+# channels of which 9 cin are real; the reference is the stride-2 convolution with K = 9 cin
+def patch_rows(x, kp, pad_value=0.0):
+    """az_im2col_s2k3: [B,C,H,W] -> [B,Ho,Wo,Kp], patches[.., t C + c] = x[2 oy - 1 + t / 3, 2 ox - 1 + t % 3, c]"""
+    b, c, h, w = x.shape
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    xp = F.pad(x, (1, 2, 1, 2))
+    taps = [xp[:, :, i:i + 2 * ho:2, j:j + 2 * wo:2] for i in range(3) for j in range(3)]  # each [B,C,Ho,Wo]
+    pt = torch.stack(taps, dim=1).reshape(b, 9 * c, ho, wo).permute(0, 2, 3, 1)
+    out = torch.full((b, ho, wo, kp), pad_value, dtype=x.dtype)
+    out[..., :9 * c] = pt
+    return out
+
+
+@pytest.mark.parametrize("cin,kp", [(3, 32), (6, 64)])
+@pytest.mark.parametrize("shape", [(2, 13, 22), (1, 16, 32), (1, 1, 1)])
+@pytest.mark.parametrize("mutant", [None, "pad_channel"])
+def test_patch_route_forward_emulation_and_its_pad_channel_mutant(cin, kp, shape, mutant, capsys):
+    """bf16x6, as the code routes it.  pad_channel: the channels [9 cin, Kp) of the patches and of the packed weights are read
+    as what lies next to them (non-zero) instead of zero"""
+    b, h, w = shape
+    cout = 32
+    geom = R.Geom2d(3, 3, 1, 2)
+    x = seeded((b, cin, h, w), 7700)
+    wt = seeded((cout, cin, 3, 3), 7701, -0.2, 0.2)
+    pr = patch_rows(x, kp)
+    w2 = torch.zeros(cout, kp)
+    w2[:, :9 * cin] = wt.permute(0, 2, 3, 1).reshape(cout, 9 * cin)
+    if mutant:
+        n = kp - 9 * cin  # (copies of the centre tap's channels: the tap no image edge zeroes)
+        pr[..., 9 * cin:] = pr[..., 4 * cin:4 * cin + n]
+        w2[:, 9 * cin:] = w2[:, 4 * cin:4 * cin + n]
+    pp, qq = R.split_parts(pr.reshape(-1, kp), "bf16x6"), R.split_parts(w2, "bf16x6")
+    acc = torch.zeros(pp[0].shape[0], cout, dtype=torch.float32)
+    for k0 in range(0, kp, 16):
+        acc = acc + sum(pp[i][:, k0:k0 + 16] @ qq[j][:, k0:k0 + 16].t() for (j, i) in TERMS["bf16x6"]).float()
+    got = acc.reshape(b, pr.shape[1], pr.shape[2], cout).permute(0, 3, 1, 2)
+    ex = R.exact("fwd", x, wt, geom=geom)
+    assert got.shape == ex["y"].shape
+    sref = R.split_reference("fwd", x, wt, "bf16x6", geom=geom)
+    r = R.check(got, "bf16x6", R.products("fwd", x, wt, geom), ex, sref)
+    with capsys.disabled():
+        print(f"\npatch route {mutant} cin {cin} {shape}: (a) {r[0]:.3g} (b) {r[1]:.3g} (c) {r[2]:.3g}")
+    assert (max(r) > 1.0) if mutant else (max(r) <= 1.0), r
+
+
+@pytest.mark.parametrize("geom", [G33, G33D2, G11, G35, R.Geom2d(3, 3, 1, 2, (7, 10)), R.Geom2d(3, 3, 1, 2, (8, 9))])
+@pytest.mark.parametrize("kind", R.KINDS)
+def test_2d_references_agree_with_a_direct_sum(kind, geom):
+    """op (torch's fp64 convolutions) against a tap-by-tap sum written here, and op_gemm against op at stride 1"""
+    b, cin, cout = 2, 3, 4
+    h, w = geom.in_hw or (7, 10)
+    st = geom.stride
+    ho, wo = (h - 1) // st + 1, (w - 1) // st + 1
+    x, wt, dy = seeded((b, cin, h, w), 7800).double(), seeded((cout, cin, geom.kh, geom.kw), 7801).double(), seeded((b, cout, ho, wo), 7802).double()
+    ph, pw = geom.pad
+    xp = F.pad(x, (pw, pw + st, ph, ph + st))
+    win = {(i, j): xp[:, :, i * geom.dil:i * geom.dil + st * ho:st, j * geom.dil:j * geom.dil + st * wo:st]
+           for i in range(geom.kh) for j in range(geom.kw)}  # x at (st oy - ph + i dil, st ox - pw + j dil): [B,cin,Ho,Wo]
+    if kind == "fwd":
+        want = sum(torch.einsum("bchw,oc->bohw", win[i, j], wt[:, :, i, j]) for (i, j) in win)
+        p, q = x, wt
+    elif kind == "wgrad":
+        want = torch.stack([torch.stack([torch.einsum("bchw,bohw->oc", win[i, j], dy) for j in range(geom.kw)], -1)
+                            for i in range(geom.kh)], -2)
+        p, q = x, dy
+    else:  # the adjoint of the forward: <fwd(x), dy> = <x, dgrad(dy)> for every x; taken from autograd of the direct sum
+        xr = x.clone().requires_grad_(True)
+        xpr = F.pad(xr, (pw, pw + st, ph, ph + st))
+        y = sum(torch.einsum("bchw,oc->bohw", xpr[:, :, i * geom.dil:i * geom.dil + st * ho:st, j * geom.dil:j * geom.dil + st * wo:st],
+                             wt[:, :, i, j]) for (i, j) in win)
+        want, = torch.autograd.grad(y, xr, dy)
+        p, q = dy, wt
+    got = R.op(kind, p, q, geom)
+    assert got.shape == want.shape
+    assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max())
+    if st == 1:
+        assert float((R.op_gemm(kind, p, q, geom) - want).abs().max()) <= 1e-13 * float(want.abs().max())

@@ -64,6 +64,15 @@ S1_CASES = [
 ]
 
 
+# The 2-D sweep against fp64 (tests/test_gpu_conv2d_fp64.py) behind the two switches that change its routes; each selection
+# also runs that file's route-coverage test under the switch.
+C2D = "tests/test_gpu_conv2d_fp64.py"
+C2D_CASES = [
+    ({"AZ_CONV2D_ROLL": "0"}, C2D, "conv_vs_fp64 and (32x or 64x) or residual_handover or every_route"),  # the roll layers on K13
+    ({"AZ_CONV2D_WGRAD_R16": "0"}, C2D, "wgrad_vs_fp64 and (32x or 64x) or accumulate_only or every_route"),  # ... on K13w
+]
+
+
 def _child(env, path, expr):
     cmd = [sys.executable, "-m", "pytest", path, "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"]
     if expr:
@@ -81,6 +90,11 @@ def test_route_behind_switch(env, path, expr):
 
 @pytest.mark.parametrize("env,path,expr", S1_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in S1_CASES])
 def test_stride1_sweep_behind_switch(env, path, expr):
+    _child(env, path, expr)
+
+
+@pytest.mark.parametrize("env,path,expr", C2D_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in C2D_CASES])
+def test_conv2d_sweep_behind_switch(env, path, expr):
     _child(env, path, expr)
 
 
