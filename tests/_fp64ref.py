@@ -24,6 +24,15 @@ Every function takes a geometry `geom`; None is the 3-D family above.  A Geom2d(
 "same" padding dil (k - 1) / 2 (3x3 d1, 3x3 d2, 1x1, 3x5; stride 2 only for the 3x3 pad-1 layer of the patch route), operands
 x: [B,cin,H,W], w: [cout,cin,kh,kw], dy: [B,cout,Ho,Wo], with K = kh kw cin (fwd), kh kw cout (dgrad), B Ho Wo (wgrad)
 (tests/test_gpu_conv2d_fp64.py).
+
+A Geom3d(stride=2, transposed, in_dhw) is one of the two strided 3x3x3 layer types of the hourglass (tests/test_gpu_conv3d_s2.py):
+    transposed = False  Conv3d(stride 2, pad 1): x fine [B,cin,D,H,W], w [cout,cin,3,3,3], dy coarse [B,cout,Dc,Hc,Wc] with
+                        Dc = (D - 1) / 2 + 1; in_dhw = the fine size where it is odd (the input gradient cannot know it)
+    transposed = True   ConvTranspose3d(stride 2, pad 1, output_padding 1): x coarse [B,cin,Dc,Hc,Wc], w [cin,cout,3,3,3],
+                        dy fine [B,cout,2Dc,2Hc,2Wc]
+K is PER OUTPUT there -- a border output of the stride-2 forward has fewer than 27 cin real products, an output of the
+transposed map 1, 2, 4 or 8 taps x channels by its parity, a weight-gradient tap the coarse positions whose fine tap lies
+inside the volume -- so products() returns the count tensor op(kind, ones, ones) and the bounds take a tensor K.
 """
 import collections
 import functools
@@ -62,6 +71,29 @@ ARITHS = ("f16x3", "bf16x6", "fp32")
 # The walking and segmented cases (batch segments of 3 images, 770 columns for 768 / 384 / 256 / 192 workgroups, 3 to 8 row
 # segments, 770 items for 200 blocks) stay below 0.13 in (b) and 0.25 in (c) but for roll64 above; check (a) peaks at 0.41
 # (f16x3 r16 AR 1, (1, 1, 1) image).
+#
+# The strided 3-D family (tests/test_gpu_conv3d_s2.py; K per output) uses the same constants; largest err / bound of checks
+# (b) / (c) measured on an MI355X at default switches per arithmetic, kind and route (the maxima sit at the outputs of the
+# smallest K: one tap x 32 channels of the transposed map, a weight-gradient tap that meets one coarse position):
+#                                              f16x3 (b)  (c)     bf16x6 (b)  (c)     fp32 (b)  (c)
+#   fwd    s2roll (plain / stats / epi)           0.19   0.50
+#   fwd    s2roll seg > 1 (V0 -> V1, B = 1)       0.22   0.60
+#   fwd    t2roll (plain / stats / epi)           0.34   0.48
+#   fwd    t2roll seg > 1 | + ragged seg          0.35   0.50 | 0.36  0.51
+#   fwd    t2 (plain / stats / epi)               0.43   0.50         0.31   0.41
+#   fwd    gather mode 1 (plain / stats / epi)    0.06   0.21         0.20   0.44       0.32   0.44
+#   fwd    gather mode 2 (plain / stats / epi)    0.64   0.85         0.36   0.44       0.92   0.59
+#   dgrad  s2roll | presplit | seg > 1            0.22   0.57 | 0.17  0.53 | 0.23  0.64
+#   dgrad  t2roll | presplit                      0.39   0.49 | 0.33  0.51
+#   dgrad  t2roll seg > 1 | + ragged seg          0.34   0.49 | 0.44  0.63
+#   dgrad  t2                                     0.58   0.66         0.45   0.57
+#   dgrad  gather mode 1                          0.07   0.18         0.11   0.29       0.36   0.47
+#   dgrad  gather mode 2                          0.76   0.95         0.49   0.58       0.70   0.48
+#   wgrad  s2r16 mask 0 | 1 | 2                   0.45   0.56 | 0.14  0.22 | 0.14  0.25
+#   wgrad  s2r16 walk, mask 0 | 1 | 2             0.05   0.24 | 0.04  0.20 | 0.05  0.22
+#   wgrad  one kd per wave                        0.42   0.52         0.29   0.38       0.42   0.23
+# Check (a) peaks at 0.40 (s2r16 mask 0 and the one-kd f16x3 weight gradient, a tap of one coarse position); the production-size
+# weight gradients (K = 195 840) stay below 0.001 in (b) and 0.03 in (c).
 C = {
     "f16x3": 2.0,   # measured max 1.17 (wide weight gradient, 64 -> 32, (1, 1, 3, 3))
     "bf16x6": 3.0,  # measured max 1.51 (r16 AR 0 weight gradient, 64 -> 64, (1, 1, 3, 3))
@@ -82,6 +114,21 @@ class Geom2d(collections.namedtuple("Geom2d", "kh kw dil stride in_hw", defaults
         return (self.dil * (self.kh - 1) // 2, self.dil * (self.kw - 1) // 2)
 
 
+class Geom3d(collections.namedtuple("Geom3d", "stride transposed in_dhw", defaults=(2, False, None))):
+    """a strided 3x3x3, pad-1 geometry (module docstring); in_dhw: (D, H, W) of the fine tensor of a stride-2 convolution where
+    the coarse size leaves it open (odd fine sizes)"""
+
+    def fine(self, coarse_dhw):
+        return tuple(self.in_dhw) if self.in_dhw is not None else tuple(2 * n for n in coarse_dhw)
+
+
+def zero_stuff(t, fine_dhw):
+    """[B,C,Dc,Hc,Wc] -> [B,C,*fine_dhw] with t at the even positions and zeros between (and behind)"""
+    z = t.new_zeros(tuple(t.shape[:2]) + tuple(fine_dhw))
+    z[:, :, ::2, ::2, ::2] = t
+    return z
+
+
 # ---- fp64 operators ---------------------------------------------------------------------------------------------------
 def _op2d(kind, p, q, g):
     st, dl = g.stride, g.dil
@@ -96,9 +143,28 @@ def _op2d(kind, p, q, g):
     return torch.nn.grad.conv2d_weight(p, (q.shape[1], p.shape[1], g.kh, g.kw), q, stride=st, padding=g.pad, dilation=dl)
 
 
+def _op3d_strided(kind, p, q, g):
+    assert g.stride == 2
+    if g.transposed:  # y = conv_transpose3d(x, w): its input gradient is the stride-2 convolution of dy with the same weight
+        if kind == "fwd":
+            return F.conv_transpose3d(p, q, stride=2, padding=1, output_padding=1)
+        if kind == "dgrad":
+            return F.conv3d(p, q, stride=2, padding=1)
+        # dW[ci][co][k] = sum_pos x[pos][ci] dy[2 pos - 1 + k][co]: the weight gradient of conv3d(dy -> x's shape)
+        return torch.nn.grad.conv3d_weight(q, (p.shape[1], q.shape[1], 3, 3, 3), p, stride=2, padding=1)
+    if kind == "fwd":
+        return F.conv3d(p, q, stride=2, padding=1)
+    if kind == "dgrad":  # the planes / rows / columns of x an odd fine size leaves without an output position of their own
+        opad = tuple(n - (2 * m - 1) for n, m in zip(g.fine(p.shape[2:]), p.shape[2:]))
+        return F.conv_transpose3d(p, q, stride=2, padding=1, output_padding=opad)
+    return torch.nn.grad.conv3d_weight(p, (q.shape[1], p.shape[1], 3, 3, 3), q, stride=2, padding=1)
+
+
 def op(kind, p, q, geom=None):
     """the fp64 operation (torch's convolutions; any device that has them)"""
     p, q = p.double(), q.double()
+    if isinstance(geom, Geom3d):
+        return _op3d_strided(kind, p, q, geom)
     if geom is not None:
         return _op2d(kind, p, q, geom)
     if kind == "fwd":
@@ -146,30 +212,65 @@ def op_gemm(kind, p, q, geom=None):
     """the same values as op(), as unfold + float64 matrix products over depth planes: no fp64 convolution of a vendor
     library is involved (the references of the large shapes are computed this way on the GPU)"""
     p, q = p.double(), q.double()
+    if isinstance(geom, Geom3d):
+        return _op_gemm3d_strided(kind, p, q, geom)
     if geom is not None:
         return _op_gemm2d(kind, p, q, geom)
+    return _op_gemm3d(kind, p, q, 1)
+
+
+def _op_gemm3d(kind, p, q, step):
+    """the stride-1 plane GEMMs.  step = 2 keeps the neighbourhood rows of the even positions only: the forward at the even
+    positions, and the weight gradient against a gradient q [B,cout,Dc,Hc,Wc] that sits at the even positions of p's volume
+    (what its zero-stuffed image would give: the rows of the stuffed zeros add nothing)"""
     if kind == "dgrad":  # conv_transpose3d(dy, w) = conv3d(dy, w with taps flipped and channels swapped)
         kind, q = "fwd", q.transpose(0, 1).flip(2, 3, 4)
     b, c, d, h, w = p.shape
+    do, ho, wo = [(n - 1) // step + 1 for n in (d, h, w)]
     xp = F.pad(p.permute(0, 2, 3, 4, 1), (0, 0, 1, 1, 1, 1, 1, 1))  # [B, D+2, H+2, W+2, C]
+
+    def rows(bi, di):
+        if step == 1:
+            return _neighbourhoods(xp, bi, di, h, w)
+        taps = [xp[bi, di * step + kd, kh:kh + h:step, kw:kw + w:step, :] for kd in range(3) for kh in range(3) for kw in range(3)]
+        return torch.stack(taps, dim=2).reshape(ho * wo, -1)
+
     if kind == "fwd":
         cout = q.shape[0]
         wm = q.permute(2, 3, 4, 1, 0).reshape(27 * c, cout)  # [(tap, ci), co]
-        y = torch.empty(b, d, h * w, cout, dtype=torch.float64, device=p.device)
+        y = torch.empty(b, do, ho * wo, cout, dtype=torch.float64, device=p.device)
         for bi in range(b):
-            for di in range(d):
-                y[bi, di] = _neighbourhoods(xp, bi, di, h, w) @ wm
-        return y.reshape(b, d, h, w, cout).permute(0, 4, 1, 2, 3)
+            for di in range(do):
+                y[bi, di] = rows(bi, di) @ wm
+        return y.reshape(b, do, ho, wo, cout).permute(0, 4, 1, 2, 3)
     cout = q.shape[1]
+    assert tuple(q.shape[2:]) == (do, ho, wo), (q.shape, (do, ho, wo))
     g = torch.zeros(cout, 27 * c, dtype=torch.float64, device=p.device)
     for bi in range(b):
-        for di in range(d):
-            g += q[bi, :, di].reshape(cout, h * w) @ _neighbourhoods(xp, bi, di, h, w)
+        for di in range(do):
+            g += q[bi, :, di].reshape(cout, ho * wo) @ rows(bi, di)
     return g.reshape(cout, 27, c).permute(0, 2, 1).reshape(cout, c, 3, 3, 3)
 
 
+def _op_gemm3d_strided(kind, p, q, g):
+    """the strided maps from the stride-1 plane GEMMs: a stride-2 convolution = the stride-1 result at the even positions; a
+    transposed one (and the input gradient of a stride-2 one) = the stride-1 convolution of the zero-stuffed operand with the
+    weight flipped and channel-swapped; the weight gradients = the stride-1 weight gradient with the coarse operand at the even
+    positions"""
+    assert g.stride == 2
+    if kind == "wgrad":  # p = x, q = dy; the result is [coarse channels, fine channels, 3, 3, 3] for both layer types
+        return _op_gemm3d("wgrad", q, p, 2) if g.transposed else _op_gemm3d("wgrad", p, q, 2)
+    if (kind == "fwd") != g.transposed:  # the stride-2 convolution of p (a transposed layer's input gradient reads w as stored)
+        return _op_gemm3d("fwd", p, q, 2)
+    return _op_gemm3d("dgrad", zero_stuff(p, g.fine(p.shape[2:])), q, 1)
+
+
 def products(kind, p, q, geom=None):
-    """K: products per output"""
+    """K: products per output (a strided 3-D geometry: the count tensor op(kind, ones, ones), broadcast over the channels)"""
+    if isinstance(geom, Geom3d):
+        one_p = torch.ones((p.shape[0], 1) + tuple(p.shape[2:]), dtype=torch.float64)
+        one_q = torch.ones((q.shape[0] if kind == "wgrad" else 1, 1) + tuple(q.shape[2:]), dtype=torch.float64)
+        return op(kind, one_p, one_q, geom) * (1 if kind == "wgrad" else p.shape[1])
     if geom is not None:
         return q.shape[0] * q.shape[2] * q.shape[3] if kind == "wgrad" else geom.kh * geom.kw * p.shape[1]
     if kind == "wgrad":
@@ -264,8 +365,33 @@ def rounding_count(arith, K, blocks=None):
         B H ceil(W / 16) blocks with non-zero products where ceil(B H W / 16) would count fewer.  `blocks` carries that number
         (wgrad_blocks_2d); every block is 3 / 6 MFMAs chained into the running accumulator (no temporary there).  The flushes:
         one atomicAdd per workgroup and output, at most one workgroup per column = (image, chunk, row segment) <= B ceil(W / 16)
-        H, within the `+ blocks` adds; the unpack copies."""
-    blocks = math.ceil(K / 16) if blocks is None else max(blocks, math.ceil(K / 16))
+        H, within the `+ blocks` adds; the unpack copies.
+
+    The strided 3-D kernels (K is a tensor there: an MFMA whose products are all padding adds an exact zero and rounds nothing,
+    so the count of an output follows its own K):
+      * az_conv3d_s2roll.hip: per (kd, kh, kw) tap one 32-deep block (cin = 32) of 3 v_mfma_f32_16x16x32 chained into the running
+        accumulator (mul4: w_hi x_hi, w_hi x_lo, w_lo x_hi), no temporary and no add; the plane-to-plane move acc[0] = acc[1]
+        is a copy.  3 per 32 products where 3 per 16 + 1 are counted.
+      * az_conv3d_t2roll.hip: a chain = the one or two ow taps of one (kd group, phase, row offset oh, 32-channel chunk): 3 or 6
+        v_mfma_f32_16x16x32 from ZERO in a temporary + one VALU add per chain and tile into the phase accumulator; the carried
+        kd = 2 set is a register copy (rotate).  An output of parity (1, 1, 1), 64 channels: 8 chains of 6 + 8 adds = 56
+        where 3 * 32 + 32 are counted.
+      * az_conv3d_t2.hip and the mode-1 / mode-2 gather kernel of az_conv3d.hip: per tap and 16-channel chunk (t2) / per tap
+        and 32-channel chunk as two 16-deep blocks (gather f16x3: 6 MFMAs from zero + one add; bf16x6: az_mfma6 / _now) -- at
+        most 3 / 6 per 16 products + one add per block, exactly what is counted; fp32: one rounding per product and add.
+      * az_conv3d_wgrad16s2.hip: a step = 32 positions = 4 coarse rows x 8 positions of one (image, coarse plane, 8-position
+        chunk) column, 3 v_mfma_f32_16x16x32 chained into the running accumulator.  Ragged rows and chunks make more steps than
+        ceil(K / 32): B Dc ceil(Hc / 4) ceil(Wc / 8) (wgrad_blocks_s2(dy, 4, 8)), passed as `blocks`; the flush is one
+        atomicAdd per persistent workgroup <= the columns B Dc ceil(Wc / 8), within the `+ blocks` adds; o_scale is a power of
+        two; the unpack copies.
+      * the stride-2 instantiations of az_conv3d_wgrad.hip (one kd per wave): one 16-position block per coarse row and
+        16-position chunk, 3 / 6 MFMAs chained into the accumulator (fp32: 2 roundings per position): B Dc Hc ceil(Wc / 16)
+        blocks (wgrad_blocks_s2(dy, 1, 16)); one atomicAdd per wave <= the (image, plane, row segment, chunk) items."""
+    if torch.is_tensor(K):  # per-output K (a strided geometry): the same count, element-wise
+        kb = torch.ceil(K / 16.0)
+        blocks = kb if blocks is None else kb.clamp_min(float(blocks))
+    else:
+        blocks = math.ceil(K / 16) if blocks is None else max(blocks, math.ceil(K / 16))
     chain = {"f16x3": 3 * blocks, "bf16x6": 6 * blocks, "fp32": 2 * K}[arith]
     return chain + blocks + 3
 
@@ -275,6 +401,13 @@ def wgrad_blocks_2d(dy):
     a gradient dy [B, C, H, W]"""
     b, _, h, w = dy.shape
     return b * h * ((w + 15) // 16)
+
+
+def wgrad_blocks_s2(coarse, rows, chunk):
+    """K blocks an output of a stride-2 / transposed weight gradient may see (rounding_count): B Dc ceil(Hc / rows)
+    ceil(Wc / chunk) for a coarse operand [B, C, Dc, Hc, Wc] -- (4, 8): az_conv3d_wgrad16s2.hip, (1, 16): az_conv3d_wgrad.hip"""
+    b, _, d, h, w = coarse.shape
+    return b * d * ((h + rows - 1) // rows) * ((w + chunk - 1) // chunk)
 
 
 def bound_a(arith, K, ex, amax_p, amax_q, blocks=None):
@@ -294,7 +427,8 @@ def bound_a(arith, K, ex, amax_p, amax_q, blocks=None):
 
 def bound_b(arith, K, ex):
     """the random-walk accumulation bound against split_reference (check b)"""
-    return C[arith] * U * (2.0 + math.sqrt(K / 32.0)) * ex["S"]
+    root = (K / 32.0).sqrt() if torch.is_tensor(K) else math.sqrt(K / 32.0)
+    return C[arith] * U * (2.0 + root) * ex["S"]
 
 
 def bound_c(arith, K, ex):
@@ -321,6 +455,8 @@ def check(got, arith, K, ex, sref, amax_p=0.0, amax_q=0.0, addend=None, blocks=N
     for its three roundings (ReLU does not increase a difference)"""
     got = got.double().to(ex["y"].device)
     y, sr = ex["y"], sref
+    if torch.is_tensor(K):
+        K = K.double().to(y.device)
     la, lb, lc = bound_a(arith, K, ex, amax_p, amax_q, blocks), bound_b(arith, K, ex), bound_c(arith, K, ex)
     if addend is not None:
         a = addend.double().to(y.device)

@@ -379,3 +379,228 @@ def test_2d_references_agree_with_a_direct_sum(kind, geom):
     assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max())
     if st == 1:
         assert float((R.op_gemm(kind, p, q, geom) - want).abs().max()) <= 1e-13 * float(want.abs().max())
+
+
+# ---- the strided 3-D family (tests/test_gpu_conv3d_s2.py) -----------------------------------------------------------------------
+S2, T2 = R.Geom3d(2, False), R.Geom3d(2, True)
+S2_FINE = [(1, 2, 2, 2), (1, 1, 6, 10), (1, 4, 6, 10), (2, 6, 8, 20), (1, 2, 10, 34), (3, 4, 18, 30), (1, 14, 50, 34)]
+S2_ODD = [(1, 7, 33, 65), (1, 3, 7, 13)]                    # fine sizes: forward and weight gradient only
+T2_COARSE = [(1, 1, 1, 1), (1, 2, 3, 5), (2, 3, 4, 17), (1, 1, 5, 9), (3, 2, 9, 15), (1, 7, 25, 17)]
+T_SEG_LEN = 2  # coarse planes per depth segment of the emulated transposed walk (the seam mutant)
+
+
+def coarse_of(fine):
+    return (fine[0],) + tuple((n - 1) // 2 + 1 for n in fine[1:])
+
+
+def geom_of(transposed, shape):
+    """the geometry of a case: shape = the fine size of a stride-2 layer / the coarse size of a transposed one"""
+    if transposed:
+        return T2
+    return R.Geom3d(2, False, shape[1:]) if any(n % 2 for n in shape[1:]) else S2
+
+
+def operands_s2(kind, transposed, shape, cin=32, cout=32, seed=7900):
+    """x: the layer's input (fine for a stride-2 layer, coarse for a transposed one), dy: the gradient of its output"""
+    b = shape[0]
+    out = tuple(2 * n for n in shape[1:]) if transposed else coarse_of(shape)[1:]
+    x = seeded((b, cin) + tuple(shape[1:]), seed)
+    wt = seeded(((cin, cout) if transposed else (cout, cin)) + (3, 3, 3), seed + 1, -0.2, 0.2)
+    dy = seeded((b, cout) + out, seed + 2) * 1e-3
+    return {"fwd": (x, wt), "dgrad": (dy, wt), "wgrad": (x, dy)}[kind]
+
+
+def rows3(t, step, edit=None):
+    """[B,C,D,H,W] (fp64) -> [B,Do,Ho,Wo,27,C]: the 27-tap neighbourhoods of the positions ::step; edit(xp) may change the
+    zero-padded channels-last volume [B,D+2,H+2,W+2,C] first"""
+    b, c, d, h, w = t.shape
+    xp = F.pad(t.permute(0, 2, 3, 4, 1), (0, 0, 1, 1, 1, 1, 1, 1)).clone()
+    if edit is not None:
+        edit(xp)
+    taps = [xp[:, kd:kd + d:step, kh:kh + h:step, kw:kw + w:step, :] for kd in range(3) for kh in range(3) for kw in range(3)]
+    return torch.stack(taps, dim=4)
+
+
+def _tap(kd, kh, kw):
+    return (kd * 3 + kh) * 3 + kw
+
+
+def emulate_s2(kind, p, q, arith, geom, mutant=None):
+    """the strided kernels' result in the emulated arithmetic: the defined products summed exactly per 32-deep K block (one tap x
+    32 channels of a convolution launch, 32 positions of a weight gradient), the block sums accumulated in fp32"""
+    terms = list(TERMS[arith])
+    if mutant == "lohi_dropped":
+        terms.remove((1, 0))
+    pp, qq = R.split_parts(p, arith), R.split_parts(q, arith)
+    if kind == "wgrad":
+        cp, fp_ = (pp, qq) if geom.transposed else (qq, pp)  # coarse = x of a transposed layer, dy of a stride-2 one
+        b, cm, dc, hc, wc = cp[0].shape
+        cn = fp_[0].shape[1]
+        m = torch.ones(b, dc, hc, wc, dtype=torch.float64)
+        if mutant == "chunk_twice":      # the ragged last 8-position chunk of every row counted twice
+            m[..., 8 * ((wc - 1) // 8):] = 2.0
+        if mutant == "rowgroup_skipped":  # the ragged last 4-row group of every plane skipped
+            m[:, :, 4 * ((hc - 1) // 4):, :] = 0.0
+        if mutant == "odd_tail_dropped":  # the last coarse plane / row / column (the one an odd fine size adds) dropped
+            m[:, dc - 1], m[:, :, hc - 1], m[..., wc - 1] = 0.0, 0.0, 0.0
+        a = [t.permute(1, 0, 2, 3, 4).reshape(cm, -1) * m.reshape(-1) for t in cp]
+        rows = [rows3(t, 2) for t in fp_]                        # [B,Dc,Hc,Wc,27,cn]
+        assert rows[0].shape[1:4] == (dc, hc, wc)
+        if mutant == "kw1_images_swapped":  # tap kw = 1 reads the odd-position image (what kw = 0 reads) instead of the even one
+            for r in rows:
+                for kd in range(3):
+                    for kh in range(3):
+                        r[..., _tap(kd, kh, 1), :] = r[..., _tap(kd, kh, 0), :]
+        bm = [r.reshape(-1, 27 * cn) for r in rows]
+        K = a[0].shape[1]
+        acc = torch.zeros(cm, 27 * cn, dtype=torch.float32)
+        for k0 in range(0, K, 32):
+            acc = acc + sum(a[i][:, k0:k0 + 32] @ bm[j][k0:k0 + 32] for (i, j) in terms).float()
+        return acc.reshape(cm, 27, cn).permute(0, 2, 1).reshape(cm, cn, 3, 3, 3)
+    if (kind == "fwd") != geom.transposed:  # a mode-1 launch: the stride-2 convolution of p
+        rows = [rows3(t, 2) for t in pp]
+        wq = qq
+    else:                                   # a mode-2 launch: the transposed convolution of p
+        fine = geom.fine(p.shape[2:])
+        dc = p.shape[2]
+
+        def edit(xp):
+            if mutant == "zero_plane_next_batch":  # behind the last coarse plane: the first plane of the next batch element
+                xp[:-1, 2 * dc + 1] = xp[1:, 1].clone()
+
+        rows = [rows3(R.zero_stuff(t, fine), 1, edit) for t in pp]
+        wq = [t.transpose(0, 1).flip(2, 3, 4) for t in qq]
+        od = torch.arange(rows[0].shape[1])
+        odd_w = torch.arange(rows[0].shape[3]) % 2 == 1
+        for r in rows:
+            if mutant == "phase_dropped":          # the (pd, ph, pw) = (0, 0, 1) phase never multiplied
+                r[:, 0::2, 0::2, 1::2] = 0.0
+            if mutant == "phase_neighbour_tap":    # the pw = 1 phases read their two kw taps the other way round
+                sw = r[:, :, :, odd_w].clone()
+                for kd in range(3):
+                    for kh in range(3):
+                        sw[..., [_tap(kd, kh, 0), _tap(kd, kh, 2)], :] = sw[..., [_tap(kd, kh, 2), _tap(kd, kh, 0)], :]
+                r[:, :, :, odd_w] = sw
+            if mutant == "seam_carry_lost":        # fine plane 2 z + 1 of the last plane z of a segment loses coarse z's kd = 2 taps
+                seam = (od % 2 == 1) & (((od - 1) // 2 + 1) % T_SEG_LEN == 0) & ((od - 1) // 2 + 1 < dc)
+                r[:, seam, :, :, :9] = 0.0         # (the flipped image's kd' = 0 = the layer's kd = 2)
+    b, do, ho, wo = rows[0].shape[:4]
+    cout = wq[0].shape[0]
+    a = [r.reshape(b * do * ho * wo, -1) for r in rows]
+    bm = [t.permute(2, 3, 4, 1, 0).reshape(-1, cout) for t in wq]
+    acc = torch.zeros(a[0].shape[0], cout, dtype=torch.float32)
+    for k0 in range(0, a[0].shape[1], 32):
+        acc = acc + sum(a[i][:, k0:k0 + 32] @ bm[j][k0:k0 + 32] for (i, j) in terms).float()
+    y = acc.reshape(b, do, ho, wo, cout).permute(0, 4, 1, 2, 3).clone()
+    if mutant == "odd_tail_dropped":
+        y[:, :, do - 1], y[:, :, :, ho - 1], y[..., wo - 1] = 0.0, 0.0, 0.0
+    return y
+
+
+def ratios_s2(kind, transposed, shape, arith, mutant=None):
+    geom = geom_of(transposed, shape)
+    p, q = operands_s2(kind, transposed, shape)
+    got = emulate_s2(kind, p, q, arith, geom, mutant)
+    ex = R.exact(kind, p, q, geom=geom)
+    assert got.shape == ex["y"].shape, (got.shape, ex["y"].shape)
+    sref = R.split_reference(kind, p, q, arith, geom=geom)
+    blocks = None
+    if kind == "wgrad":
+        blocks = R.wgrad_blocks_s2(p if transposed else q, 4, 8)
+    return R.check(got, arith, R.products(kind, p, q, geom), ex, sref, R.amax_of(p), R.amax_of(q), blocks=blocks)
+
+
+_EMU_S2 = [(False, s, k) for s in S2_FINE for k in R.KINDS] + [(False, s, k) for s in S2_ODD for k in ("fwd", "wgrad")]
+_EMU_S2 += [(True, s, k) for s in T2_COARSE for k in R.KINDS]
+
+
+@pytest.mark.parametrize("transposed,shape,kind", _EMU_S2, ids=[f"{'t2' if t else 's2'}-{k}-{s}" for (t, s, k) in _EMU_S2])
+@pytest.mark.parametrize("arith", ["f16x3", "bf16x6", "fp32"])
+def test_emulated_strided_arithmetic_passes_the_checks(arith, transposed, shape, kind, capsys):
+    r = ratios_s2(kind, transposed, shape, arith)
+    with capsys.disabled():
+        print(f"\nemulated {'transposed' if transposed else 'stride-2'} {arith} {kind} {shape}: (a) {r[0]:.4f} (b) {r[1]:.4f} (c) {r[2]:.4f}")
+    assert max(r) <= 1.0, r
+
+
+# the launches of the transposed map: the forward of a transposed layer (shape = coarse) and the input gradient of a stride-2
+# one (shape = fine)
+_MODE2 = [(True, s, "fwd") for s in T2_COARSE] + [(False, s, "dgrad") for s in S2_FINE]
+
+
+def _coarse_dhw(transposed, shape):
+    return shape[1:] if transposed else coarse_of(shape)[1:]
+
+
+_WG = [(t, s, "wgrad") for t, shapes in ((False, S2_FINE + S2_ODD), (True, T2_COARSE)) for s in shapes]
+MUTANTS_S2 = [  # (mutant, arithmetics, cases (transposed, shape, kind) it applies to)
+    ("phase_dropped", R.ARITHS, _MODE2),
+    ("phase_neighbour_tap", R.ARITHS, _MODE2),
+    ("seam_carry_lost", R.ARITHS, [c for c in _MODE2 if _coarse_dhw(c[0], c[1])[0] > T_SEG_LEN]),
+    ("zero_plane_next_batch", R.ARITHS, [c for c in _MODE2 if c[1][0] >= 2]),
+    ("odd_tail_dropped", R.ARITHS, [(False, s, k) for s in S2_ODD for k in ("fwd", "wgrad")]),
+    ("kw1_images_swapped", R.ARITHS, [c for c in _WG if not c[0]] + [c for c in _WG if c[0]]),
+    ("chunk_twice", R.ARITHS, [c for c in _WG if _coarse_dhw(c[0], c[1])[2] % 8]),
+    ("rowgroup_skipped", R.ARITHS, [c for c in _WG if _coarse_dhw(c[0], c[1])[1] % 4]),
+    ("lohi_dropped", ("f16x3",), [(t, s, k) for (t, s, k) in _EMU_S2]),
+]
+_CASES_S2 = [(m, a, t, s, k) for (m, ariths, cases) in MUTANTS_S2 for a in ariths for (t, s, k) in cases]
+
+
+@pytest.mark.parametrize("mutant,arith,transposed,shape,kind", _CASES_S2,
+                         ids=[f"{m}-{a}-{'t2' if t else 's2'}-{k}-{s}" for (m, a, t, s, k) in _CASES_S2])
+def test_strided_mutant_fails_a_check(mutant, arith, transposed, shape, kind, capsys):
+    r = ratios_s2(kind, transposed, shape, arith, mutant)
+    with capsys.disabled():
+        print(f"\nstrided mutant {mutant} {arith} {kind} {shape}: (a) {r[0]:.3g} (b) {r[1]:.3g} (c) {r[2]:.3g}")
+    assert max(r) > 1.0, r
+
+
+_AGREE = [(False, (2, 4, 6, 10)), (False, (1, 7, 5, 9)), (False, (1, 1, 6, 10)), (True, (2, 3, 4, 5)), (True, (1, 1, 3, 5))]
+
+
+@pytest.mark.parametrize("transposed,shape", _AGREE, ids=[f"{'t2' if t else 's2'}-{s}" for (t, s) in _AGREE])
+@pytest.mark.parametrize("kind", R.KINDS)
+def test_strided_gemm_reference_is_the_convolution(kind, transposed, shape):
+    """op_gemm on the strided geometries (an odd fine size and D = 1 among them) computes what torch's fp64 convolutions do"""
+    geom = geom_of(transposed, shape)
+    p, q = operands_s2(kind, transposed, shape, cin=32, cout=64)
+    want, got = R.op(kind, p, q, geom), R.op_gemm(kind, p, q, geom)
+    assert got.shape == want.shape
+    assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max())
+
+
+@pytest.mark.parametrize("transposed,fine", [(False, (4, 6, 8)), (False, (5, 7, 3)), (True, (4, 6, 8))])
+def test_strided_references_agree_with_a_direct_sum(transposed, fine):
+    """op on the strided geometries against a seven-loop sum over (b, co, ci, coarse position, tap) written here: with
+    f = 2 c - 1 + k,  stride-2: y[b,co,c] += x[b,ci,f] w[co,ci,k];  transposed: y[b,co,f] += x[b,ci,c] w[ci,co,k]"""
+    b, cin, cout = 2, 2, 3
+    coarse = tuple((n - 1) // 2 + 1 for n in fine)
+    geom = R.Geom3d(2, transposed, None if transposed else fine)
+    xs, ys = (coarse, fine) if transposed else (fine, coarse)
+    x, dy = seeded((b, cin) + xs, 7990).double(), seeded((b, cout) + ys, 7992).double()
+    wt = seeded(((cin, cout) if transposed else (cout, cin)) + (3, 3, 3), 7991).double()
+    y, dx, dw = torch.zeros_like(dy), torch.zeros_like(x), torch.zeros_like(wt)
+    K = {k: torch.zeros_like(t) for k, t in (("fwd", dy), ("dgrad", x), ("wgrad", wt))}
+    for bi in range(b):
+        for co in range(cout):
+            for ci in range(cin):
+                for c in [(i, j, l) for i in range(coarse[0]) for j in range(coarse[1]) for l in range(coarse[2])]:
+                    for k in [(i, j, l) for i in range(3) for j in range(3) for l in range(3)]:
+                        f = tuple(2 * ci_ - 1 + ki for ci_, ki in zip(c, k))
+                        if any(v < 0 or v >= n for v, n in zip(f, fine)):
+                            continue
+                        xi, yi = ((bi, ci) + c, (bi, co) + f) if transposed else ((bi, ci) + f, (bi, co) + c)
+                        wi = ((ci, co) if transposed else (co, ci)) + k
+                        y[yi] += x[xi] * wt[wi]
+                        dx[xi] += dy[yi] * wt[wi]
+                        dw[wi] += x[xi] * dy[yi]
+                        K["fwd"][yi] += 1
+                        K["dgrad"][xi] += 1
+                        K["wgrad"][wi] += 1
+    for kind, (p, q), want in (("fwd", (x, wt), y), ("dgrad", (dy, wt), dx), ("wgrad", (x, dy), dw)):
+        got = R.op(kind, p, q, geom)
+        assert got.shape == want.shape, kind
+        assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max()), kind
+        assert float((R.op_gemm(kind, p, q, geom) - want).abs().max()) <= 1e-13 * float(want.abs().max()), kind
+        assert torch.equal(R.products(kind, p, q, geom).expand_as(want), K[kind]), kind  # the count tensor: products per output

@@ -377,9 +377,10 @@ def _sample_points(b, d, h, w, n_random, seed):
     return torch.cat(pts).to(DEV)
 
 
-def _sampled_reference(p_cl, wt, pts, chunk=16384):
+def _sampled_reference(p_cl, wt, pts, chunk=16384, ones_cl=None):
     """fp64 y / S / Q2 / sum_q / sum_p / f16x3 split reference of a stride-1 forward at the voxels `pts`, each from its 27-tap
-    neighbourhood (p_cl: [B,D,H,W,C] on the GPU, wt: [cout,cin,3,3,3])"""
+    neighbourhood (p_cl: [B,D,H,W,C] on the GPU, wt: [cout,cin,3,3,3]).  ones_cl: the positions of p_cl that hold an operand
+    value where not all do (a zero-stuffed volume, tests/test_gpu_conv3d_s2.py)"""
     c, cout = p_cl.shape[-1], wt.shape[0]
     offs = torch.tensor([[0, kd, kh, kw] for kd in range(3) for kh in range(3) for kw in range(3)], device=DEV)
     wm = wt.double().to(DEV).permute(2, 3, 4, 1, 0).reshape(27 * c, cout)
@@ -387,7 +388,7 @@ def _sampled_reference(p_cl, wt, pts, chunk=16384):
     pad = lambda t: torch.nn.functional.pad(t, (0, 0, 1, 1, 1, 1, 1, 1))  # noqa: E731
     hp, lp = [pad(t.permute(0, 2, 3, 4, 1)) for t in R.split_parts(p_cl.permute(0, 4, 1, 2, 3), "f16x3")]
     xp = pad(p_cl.double())
-    ones = pad(torch.ones_like(p_cl, dtype=torch.float64))
+    ones = pad(torch.ones_like(p_cl, dtype=torch.float64) if ones_cl is None else ones_cl.double())
     keys = ("y", "S", "Q2", "sum_q", "sum_p", "sref")
     out = {k: [] for k in keys}
     for i in range(0, pts.shape[0], chunk):

@@ -73,6 +73,24 @@ C2D_CASES = [
 ]
 
 
+# The strided sweep against fp64 (tests/test_gpu_conv3d_s2.py) behind every switch that changes one of its routes; each
+# selection also runs that file's route-coverage test under the switch (which asserts, for the AZ_S2ROLL_SEGLEN rows, that
+# multi-plane and ragged segments are among the cases).
+S2 = "tests/test_gpu_conv3d_s2.py"
+S2_MODE1_3264 = "f16x3 and (s2-fwd-32x64 or t2-dgrad-64x32) or every_route"   # the launches of mode 1, 32 -> 64
+S2_MODE2_6432 = "f16x3 and (t2-fwd-64x32 or s2-dgrad-32x64) or every_route"   # the launches of mode 2, 64 -> 32
+S2_MULTI_TILE = "2x6x8x20 or 3x4x18x30 or 1x14x50x34 or 2x3x4x17 or 3x2x9x15 or 1x7x25x17"
+S2_CASES = [
+    ({"AZ_CONV_S2ROLL": "0"}, S2, S2_MODE1_3264),                 # ... on the gather kernel
+    ({"AZ_CONV_T2ROLL": "0"}, S2, S2_MODE2_6432),                 # ... on az_conv3d_t2.hip
+    ({"AZ_WGRAD_S2R16": "0"}, S2, "wgrad and f16x3 or accumulate_only or every_route"),  # f16x3 weight gradients, one kd per wave
+    ({"AZ_S2ROLL_SEGLEN": "3"}, S2, S2_MODE1_3264),               # multi-plane segments, ragged where Do % 3
+    ({"AZ_S2ROLL_SEGLEN": "2"}, S2, S2_MODE1_3264),
+    ({"AZ_CONV_MAP": "0"}, S2, f"strided_vs_fp64 and not wgrad and ({S2_MULTI_TILE}) or every_route"),  # linear block -> tile map
+    ({"AZ_PRESPLIT": "0"}, S2, "presplit or accumulate_only or every_route"),  # the pre-split tests skip, the rest pass
+]
+
+
 def _child(env, path, expr):
     cmd = [sys.executable, "-m", "pytest", path, "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"]
     if expr:
@@ -95,6 +113,11 @@ def test_stride1_sweep_behind_switch(env, path, expr):
 
 @pytest.mark.parametrize("env,path,expr", C2D_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in C2D_CASES])
 def test_conv2d_sweep_behind_switch(env, path, expr):
+    _child(env, path, expr)
+
+
+@pytest.mark.parametrize("env,path,expr", S2_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in S2_CASES])
+def test_strided_sweep_behind_switch(env, path, expr):
     _child(env, path, expr)
 
 
