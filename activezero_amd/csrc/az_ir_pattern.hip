@@ -100,6 +100,9 @@ __device__ __forceinline__ void area_up(int d, int ssize, int dsize, int &s, flo
     f = fx;
 }
 
+// MODE 2: get_smoothed_ir_pattern2 (d - avg > threshold); MODE 1: get_smoothed_ir_pattern (d > avg, compared directly:
+// a difference that flushes to zero must not change the answer); MODE 0: get_ir_pattern (d > threshold, avg unused)
+template <int MODE>
 __global__ void __launch_bounds__(256)
 irp_pattern_kernel(float *__restrict__ out, const float *__restrict__ avg, const unsigned *__restrict__ mm,
                    const float *__restrict__ a, const float *__restrict__ b, int H, int W, int hs, int ws,
@@ -109,6 +112,10 @@ irp_pattern_kernel(float *__restrict__ out, const float *__restrict__ avg, const
     const int y = idx / W, x = idx - y * W, img = blockIdx.y;
     const float mn = __uint_as_float(mm[2 * img]), mx = __uint_as_float(mm[2 * img + 1]);
     const float d = (fabsf(a[(size_t)img * H * W + idx] - b[(size_t)img * H * W + idx]) - mn) / (mx - mn);
+    if constexpr (MODE == 0) {
+        out[(size_t)img * H * W + idx] = (d > threshold) ? 1.f : 0.f;
+        return;
+    }
     int sy, sx;
     float fy, fx;
     area_up(y, hs, H, sy, fy);
@@ -119,7 +126,10 @@ irp_pattern_kernel(float *__restrict__ out, const float *__restrict__ avg, const
     const float r0 = p[sy * ws + sx] * (1.f - fx) + p[sy * ws + sx1] * fx;
     const float r1 = p[sy1 * ws + sx] * (1.f - fx) + p[sy1 * ws + sx1] * fx;
     const float v = r0 * (1.f - fy) + r1 * fy;
-    out[(size_t)img * H * W + idx] = (d - v > threshold) ? 1.f : 0.f;
+    if constexpr (MODE == 1)
+        out[(size_t)img * H * W + idx] = (d > v) ? 1.f : 0.f;
+    else
+        out[(size_t)img * H * W + idx] = (d - v > threshold) ? 1.f : 0.f;
 }
 
 extern "C" long long az_ir_pattern_workspace(int B, int H, int W, int ks) {
@@ -142,7 +152,37 @@ extern "C" int az_ir_pattern(float *pattern, float *workspace, long long workspa
     hipLaunchKernelGGL(irp_minmax_kernel, dim3(min((hw + 255) / 256, 256), B), dim3(256), 0, s, mm, img_ir, img, hw);
     hipLaunchKernelGGL(irp_shrink_kernel, dim3((hs * ws + 255) / 256, B), dim3(256), 0, s, avg, mm, img_ir, img, H, W,
                        hs, ws);
-    hipLaunchKernelGGL(irp_pattern_kernel, dim3((hw + 255) / 256, B), dim3(256), 0, s, pattern, avg, mm, img_ir, img,
+    hipLaunchKernelGGL(irp_pattern_kernel<2>, dim3((hw + 255) / 256, B), dim3(256), 0, s, pattern, avg, mm, img_ir, img,
+                       H, W, hs, ws, threshold);
+    return az_launch_status();
+}
+
+// get_ir_pattern (mode 0, dataset_utils.py:12-17) and get_smoothed_ir_pattern (mode 1, :20-30) on the kernels above
+extern "C" int az_ir_pattern_mode(float *pattern, float *workspace, long long workspace_bytes, const float *img_ir,
+                                  const float *img, int B, int H, int W, int ks, float threshold, int mode, void *stream) {
+    if (pattern == nullptr || workspace == nullptr || img_ir == nullptr || img == nullptr) return AZ_EINVAL;
+    if (mode != 0 && mode != 1) return AZ_EINVAL;
+    if (B <= 0 || H <= 0 || W <= 0) return AZ_EINVAL;
+    if ((long long)H * W > 0x7fffffffLL || B > 65535) return AZ_EUNSUPPORTED;
+    // mode 0 smooths nothing: ks is ignored and the workspace holds the min / max words alone
+    const long long need = mode == 0 ? ((long long)B * 2) * 4 + 64 : az_ir_pattern_workspace(B, H, W, ks);
+    if (need < 0) return AZ_EINVAL;
+    if (workspace_bytes < need) return AZ_EWORKSPACE;
+    hipStream_t s = az_stream(stream);
+    unsigned *mm = reinterpret_cast<unsigned *>(workspace);
+    const int hw = H * W;
+    hipLaunchKernelGGL(irp_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, mm, B);
+    hipLaunchKernelGGL(irp_minmax_kernel, dim3(min((hw + 255) / 256, 256), B), dim3(256), 0, s, mm, img_ir, img, hw);
+    if (mode == 0) {
+        hipLaunchKernelGGL(irp_pattern_kernel<0>, dim3((hw + 255) / 256, B), dim3(256), 0, s, pattern, (const float *)nullptr, mm,
+                           img_ir, img, H, W, 1, 1, threshold);
+        return az_launch_status();
+    }
+    float *avg = workspace + 16 + 2 * B;
+    const int hs = H / ks, ws = W / ks;
+    hipLaunchKernelGGL(irp_shrink_kernel, dim3((hs * ws + 255) / 256, B), dim3(256), 0, s, avg, mm, img_ir, img, H, W,
+                       hs, ws);
+    hipLaunchKernelGGL(irp_pattern_kernel<1>, dim3((hw + 255) / 256, B), dim3(256), 0, s, pattern, avg, mm, img_ir, img,
                        H, W, hs, ws, threshold);
     return az_launch_status();
 }

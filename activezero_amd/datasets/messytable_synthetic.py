@@ -10,6 +10,10 @@ runs end to end without the dataset:
   img_disp_L / img_disp_R          [1,2H,2W] disparity at the 2x resolution of the depth maps (messytable.py:252-261)
   img_depth_L / img_depth_R        [1,2H,2W] metres;  focal_length, baseline [1,1,1];  prefix (str)
   (onReal) img_real_L / img_real_R [3,H,W],  img_real_L_reproj / img_real_R_reproj [1,H,W]
+  (onReal, temporal=True) the two real patterns are the reference's TEMPORAL patterns (tools/temporal_ir.py:91-114, read
+                                             back by messytable.py:406-426): per view a stack of 7 projector exposures
+                                             [7,H,W] uint8 is rendered -- exposure k = texture + (k/6) dot gain + sensor
+                                             noise, quantised to 0..255 -- and passed through get_temporal_ir_pattern
 
 Geometry: a smooth random depth field -> disparity = focal * baseline / depth; the right view is the left one
 moved by the (integer-rounded) disparity with the scatter warp K1, so disparity, images and patterns are
@@ -17,7 +21,7 @@ mutually consistent and the losses have signal."""
 import torch
 import torch.nn.functional as F
 
-from activezero_amd.datasets.dataset_utils_gpu import get_smoothed_ir_pattern2
+from activezero_amd.datasets.dataset_utils_gpu import get_smoothed_ir_pattern2, get_temporal_ir_pattern
 from activezero_amd.utils.warp_ops import apply_disparity_cu
 
 _MEAN = (0.485, 0.456, 0.406)
@@ -25,7 +29,9 @@ _STD = (0.229, 0.224, 0.225)
 
 
 class SyntheticMessytableDataset(torch.utils.data.Dataset):
-    def __init__(self, length=64, height=256, width=512, onReal=True, device="cuda:0", seed=0, max_disp=192):
+    def __init__(self, length=64, height=256, width=512, onReal=True, device="cuda:0", seed=0, max_disp=192,
+                 temporal=False):
+        self.temporal = bool(temporal)
         self.length, self.h, self.w, self.onReal = int(length), int(height), int(width), bool(onReal)
         self.device, self.seed, self.max_disp = torch.device(device), int(seed), int(max_disp)
         self.focal_length, self.baseline = 446.31, 0.055  # the order of the MessyTable rig (metres, half-res pixels)
@@ -63,6 +69,26 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
         std = torch.tensor(_STD, device=self.device).view(3, 1, 1)
         return ((rgb - mean) / std).contiguous()
 
+    def _real_views(self, idx):
+        """the real item's generator, noisy (left, right), their no-IR versions and the noise-free lit pair [2,H,W]"""
+        g = self._gen(idx, 2)
+        rl, rr, rl0, rr0, *_ = self._views(g)
+        lit = torch.stack([rl, rr])
+        noise = lambda im: (im + 0.02 * torch.randn(im.shape, device=self.device, generator=g)).clamp(0, 1)
+        return g, noise(rl), noise(rr), rl0, rr0, lit
+
+    def _exposures(self, g, lit, unlit, frames=7, sigma=1.5):
+        """[2,frames,H,W] uint8: both views at projector power k / (frames - 1), sensor noise of `sigma` grey levels"""
+        power = torch.linspace(0, 1, frames, device=self.device).view(1, frames, 1, 1)
+        level = 255.0 * (unlit[:, None] + power * (lit - unlit)[:, None])
+        level = level + sigma * torch.randn(level.shape, device=self.device, generator=g)
+        return level.round().clamp(0, 255).to(torch.uint8)
+
+    def _temporal_stack(self, idx):
+        """the exposure stack item `idx` takes its real patterns from (temporal=True); for tests"""
+        g, _, _, rl0, rr0, lit = self._real_views(idx)
+        return self._exposures(g, lit, torch.stack([rl0, rr0]))
+
     def __getitem__(self, idx):
         g = self._gen(idx, 1)
         left, right, left0, right0, disp2, depth2, disp_r2, depth_r2 = self._views(g)
@@ -77,11 +103,11 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
             "baseline": torch.full((1, 1, 1), self.baseline, device=self.device),
         }
         if self.onReal:
-            g = self._gen(idx, 2)
-            rl, rr, rl0, rr0, *_ = self._views(g)
-            noise = lambda im: (im + 0.02 * torch.randn(im.shape, device=self.device, generator=g)).clamp(0, 1)
-            rl, rr = noise(rl), noise(rr)
-            rpat = get_smoothed_ir_pattern2(torch.stack([rl, rr]), torch.stack([rl0, rr0]))
+            g, rl, rr, rl0, rr0, lit = self._real_views(idx)
+            if self.temporal:
+                rpat = get_temporal_ir_pattern(self._exposures(g, lit, torch.stack([rl0, rr0])))
+            else:
+                rpat = get_smoothed_ir_pattern2(torch.stack([rl, rr]), torch.stack([rl0, rr0]))
             item.update({"img_real_L": self._normalise(rl), "img_real_R": self._normalise(rr),
                          "img_real_L_reproj": rpat[0:1].contiguous(), "img_real_R_reproj": rpat[1:2].contiguous()})
         return item

@@ -541,6 +541,26 @@ int az_col2im_s2k3(float *grad_x, const float *grad_patches, int B, int C, int H
 long long az_ir_pattern_workspace(int B, int H, int W, int ks);
 int az_ir_pattern(float *pattern, float *workspace, long long workspace_bytes, const float *img_ir,
                   const float *img, int B, int H, int W, int ks, float threshold, void *stream);
+/* the two plainer helpers of the same file on the same kernels.  mode 0: datasets/dataset_utils.py:12-17 get_ir_pattern,
+ * pattern = normalised |img_ir - img| > threshold, no smoothing (ks is ignored; 8 B + 64 workspace bytes suffice).
+ * mode 1: datasets/dataset_utils.py:20-30 get_smoothed_ir_pattern, pattern = normalised difference > its INTER_AREA
+ * round trip, the two compared directly (threshold is ignored; workspace of az_ir_pattern_workspace() bytes).
+ * A null pointer or another mode: AZ_EINVAL. */
+int az_ir_pattern_mode(float *pattern, float *workspace, long long workspace_bytes, const float *img_ir,
+                       const float *img, int B, int H, int W, int ks, float threshold, int mode, void *stream);
+
+/* ---- K17: temporal IR pattern (data side; az_temporal_ir.hip) -----------------------------
+ * replaces the offline pass tools/temporal_ir.py:91-114 with its helper get_smoothed_ir_pattern (:35-40): per pixel the
+ * least-squares line over the T projector exposures of a view, diff = |fit[T-1] - fit[0]| / 255 min-max normalised over
+ * the image, pattern = 1 where diff exceeds its cv2.blur(ks x ks) -- the normalised box filter, BORDER_REFLECT_101 --
+ * by more than `threshold`, else 0; an image whose diff is constant yields all zeros (the reference's NaN comparisons).
+ * stack: [B,T,H,W] grey levels 0..255, f32 or (stack_is_u8 != 0) uint8; pattern: [B,H,W] f32; workspace of
+ * az_temporal_ir_workspace() bytes (the diff image, and the min / max words of each image on a 256-byte line).
+ * 2 <= T <= 16 and ks odd in [3, 31], else AZ_EUNSUPPORTED; H, W > ks / 2 (one reflection per border), else AZ_EINVAL;
+ * a null pointer: AZ_EINVAL; the workspace query returns the same codes. */
+long long az_temporal_ir_workspace(int B, int T, int H, int W, int ks);
+int az_temporal_ir(float *pattern, float *workspace, long long workspace_bytes, const void *stack,
+                   int stack_is_u8, int B, int T, int H, int W, int ks, float threshold, void *stream);
 
 /* ---- K10/K11: RAFT-Stereo 1-D correlation (secondary path) -----------------------
  * replaces nets/raft/corr.py:115-161 (CorrBlock1D: einsum all-pairs correlation /

@@ -5,7 +5,10 @@ ALGORITHMIC bytes of SURVEY.md 8(d).  Prints a markdown table (DESIGN.md section
 
     python tools/bench_aux_kernels.py raft_head [out.json]
 runs the RAFT-Stereo prediction head instead (K15 convex upsampling + K16 sequence loss, 22 iterations forward and
-backward at mask [4,144,136,240]) beside the reference's arithmetic in PyTorch eager, and prints one JSON record."""
+backward at mask [4,144,136,240]) beside the reference's arithmetic in PyTorch eager, and prints one JSON record.
+
+    python tools/bench_aux_kernels.py temporal_ir [out.json]
+runs the temporal IR pattern (K17) at B=8, T=7, 540x960, ks=11 for uint8 and float32 stacks and prints one JSON record."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -122,6 +125,60 @@ def raft_head(out_path=None):
             fh.write(json.dumps(rec, indent=1) + "\n")
 
 
+def temporal_ir(out_path=None):
+    import json
+    import statistics
+    import bench as _bench
+    from activezero_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    B, T, H, W, ks, sets, reps = 8, 7, 540, 960, 11, 8, 20
+    g = torch.Generator(device=dev).manual_seed(0)
+    ws_bytes = _lib.lib().az_temporal_ir_workspace(B, T, H, W, ks)
+    rec = {"case": "temporal_ir", "stack": [B, T, H, W], "ks": ks, "threshold": 0.005,
+           "timing": "%d launches on %d rotated buffer sets (more than the 256 MiB cache) per event pair, median of %d"
+                     % (sets, sets, reps)}
+    for name, dtype, size in (("u8", torch.uint8, 1), ("f32", torch.float32, 4)):
+        stacks = []
+        for _ in range(sets):  # texture + k * dot gain + noise, as a loader renders it
+            tex = 20 + 100 * torch.rand(B, 1, H, W, device=dev, generator=g)
+            gain = (torch.rand(B, 1, H, W, device=dev, generator=g) < 0.06) * 15.0
+            k = torch.arange(T, device=dev).view(1, T, 1, 1)
+            stacks.append((tex + gain * k + 1.5 * torch.randn(B, T, H, W, device=dev, generator=g)).round().clamp(0, 255).to(dtype))
+        wss = [torch.empty(ws_bytes // 4, device=dev) for _ in range(sets)]
+        outs = [torch.empty(B, H, W, device=dev) for _ in range(sets)]
+
+        def launch(i):
+            ops._call("az_temporal_ir", outs[i].data_ptr(), wss[i].data_ptr(), ws_bytes, stacks[i].data_ptr(), int(size == 1),
+                      B, T, H, W, ks, 0.005, ops._stream())
+
+        for _ in range(2):
+            for i in range(sets):
+                launch(i)
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(sets):
+                launch(i)
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / sets)
+        m = statistics.median(ms)
+        nbytes = float(B) * H * W * (T * size + 4 + 4 + 4)  # stack read, diff write, diff read, pattern write
+        rec[name] = {"ms": m, "min_ms": min(ms), "algorithmic_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6,
+                     "share_of_ones": float(outs[0].mean())}
+        del stacks, wss, outs
+    rec["copy_probe_GB/s"] = _bench.hbm_probe(dev)["GB/s"]
+    for name in ("u8", "f32"):
+        rec[name]["of_copy_probe"] = rec[name]["GB/s"] / rec["copy_probe_GB/s"]
+    print(json.dumps(rec))
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(rec, indent=1) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "temporal_ir":
+    temporal_ir(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "raft_head":
     raft_head(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
