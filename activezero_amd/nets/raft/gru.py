@@ -99,8 +99,9 @@ def _source(t):
     if t.shape[1] <= 128:
         # an image the kernel can transpose on the way -- unless it is the same tensor as last time: then a cached copy is cheaper
         key = cache_key(t)
-        seen = cache_get(_SEEN_ONCE, key)
-        if (seen is None or seen[0]() is not t) and cache_get(_ROWS_CACHE, key) is None:
+        seen, rows = cache_get(_SEEN_ONCE, key), cache_get(_ROWS_CACHE, key)
+        # (an entry left by a dead tensor whose address this one has recycled answers for neither)
+        if (seen is None or seen[0]() is not t) and (rows is None or rows[1]() is not t):
             cache_put(_SEEN_ONCE, key, (weakref.ref(t),), 8)
             return t, 1
     return _cached_rows(t), 0

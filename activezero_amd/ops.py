@@ -320,6 +320,78 @@ def disp_metrics(disp_gt, depth_gt, disp_pred, mask, focal_x_baseline=None, dept
 
 
 # ----------------------------------------------------------------------------
+# K18 ground truth from the right view, K19 error colour images
+# ----------------------------------------------------------------------------
+def gt_from_right(disp_r, extra=None, keep=None, *, scale_factor=0.5, size=None, lo=0.0, hi=float("inf"), check=False):
+    """train.py:255-272 / test.py:91-110 in one launch: nearest resize of the right view's disparity disp_r [N,1,Hin,Win]
+    (by scale_factor, or to size=(H, W)), truncation to an integer shift, scatter to the left view (smallest source column
+    wins, holes 0) and the mask lo < disp_l < hi.  extra [N,Ce,Hin,Win]: channels warped by the same shifts; keep
+    [N,Ck,Hin,Win]: channels resized only.  Returns (disp_l, extra_l, keep_s, mask, stats): extra_l / keep_s are None where
+    the input was; mask is a bool view of the byte tensor the kernel wrote; stats is an int32 device tensor
+    [number of disparities that are <= -1 or not finite, number of mask pixels].  No host sync -- unless check=True, which
+    reads stats[0] and raises AssertionError as the reference's sign assertion would."""
+    d = _chk(disp_r, "disp_r")
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise RuntimeError("disp_r must be [N,1,H,W]")
+    n, _, hin, win = d.shape
+    chans = []
+    for t, name in ((extra, "extra"), (keep, "keep")):
+        if t is not None:
+            _chk(t, name)
+            if t.dim() != 4 or t.shape[0] != n or tuple(t.shape[2:]) != (hin, win) or t.device != d.device:
+                raise RuntimeError(f"{name}: shape {tuple(t.shape)} does not match disp_r {tuple(d.shape)}")
+        chans.append(0 if t is None else t.shape[1])
+    ce, ck = chans
+    if size is not None:  # ATen: scale = in / out in float when a size is given
+        h, w = (int(s) for s in size)
+        if h < 1 or w < 1:
+            raise RuntimeError(f"size {tuple(size)} must be positive")
+        scale_h, scale_w = hin / h, win / w
+    else:  # ... and 1 / scale_factor with recompute_scale_factor=False; the output size is floor(in * scale_factor)
+        sh, sw = scale_factor if isinstance(scale_factor, (tuple, list)) else (scale_factor, scale_factor)
+        h, w = int(hin * float(sh)), int(win * float(sw))
+        scale_h, scale_w = 1.0 / float(sh), 1.0 / float(sw)
+    disp_l = d.new_empty(n, 1, h, w)
+    extra_l = d.new_empty(n, ce, h, w) if ce else None
+    keep_s = d.new_empty(n, ck, h, w) if ck else None
+    mask = torch.empty(n, 1, h, w, dtype=torch.uint8, device=d.device)
+    stats = torch.zeros(2, dtype=torch.int32, device=d.device)
+    with torch.cuda.device(d.device):
+        _call("az_gt_from_right", _p(disp_l), _p(extra_l), _p(keep_s), _p(mask), _p(stats), _p(d), _p(extra), _p(keep),
+              n, ce, ck, hin, win, h, w, scale_h, scale_w, float(lo), float(hi), _stream())
+    if check:  # the one host sync, on request
+        bad = int(stats[0])
+        if bad:
+            raise AssertionError(f"gt_from_right: {bad} disparities are <= -1 or not finite (warp_ops.py:73-77 asserts one sign)")
+    return disp_l, extra_l, keep_s, mask.view(torch.bool), stats
+
+
+def error_img(est, gt, mask, kind="disp", abs_thres=None, rel_thres=0.05, channels_first=True):
+    """utils/util.py:185-244 for every image of a batch, on the device: est, gt, mask of one shape with B * H * W elements
+    ([B,H,W] or [B,1,H,W]; mask bool or uint8) -> [B,3,H,W] (channels_first, train.py:354-356) or [B,H,W,3] float32.
+    kind "disp" (abs_thres 3.0, rel_thres 0.05) or "depth" (abs_thres 1.0).  No host sync."""
+    if kind not in ("disp", "depth"):
+        raise RuntimeError(f"kind must be 'disp' or 'depth', got {kind!r}")
+    e = _chk(est, "est")
+    g = _chk(gt, "gt")
+    if e.shape != g.shape:
+        raise RuntimeError(f"est {tuple(e.shape)} and gt {tuple(g.shape)} must have identical shapes")
+    if mask is None:
+        raise RuntimeError("mask is required")
+    m = _mask_u8(mask, g)
+    if not (e.dim() == 3 or (e.dim() == 4 and e.shape[1] == 1)):
+        raise RuntimeError("est, gt and mask must be [B,H,W] or [B,1,H,W]")
+    b, (h, w) = e.shape[0], e.shape[-2:]
+    if abs_thres is None:
+        abs_thres = 3.0 if kind == "disp" else 1.0
+    out = e.new_empty((b, 3, h, w) if channels_first else (b, h, w, 3))
+    with torch.cuda.device(e.device):
+        _call("az_error_img", _p(out), _p(e), _p(g), _p(m), 0 if kind == "disp" else 1, float(abs_thres), float(rel_thres),
+              1 if channels_first else 0, b, h, w, _stream())
+    return out
+
+
+# ----------------------------------------------------------------------------
 # K15 RAFT-Stereo convex upsampling
 # ----------------------------------------------------------------------------
 def _chk_mask(mask, name="mask"):

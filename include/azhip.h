@@ -562,6 +562,46 @@ long long az_temporal_ir_workspace(int B, int T, int H, int W, int ks);
 int az_temporal_ir(float *pattern, float *workspace, long long workspace_bytes, const void *stack,
                    int stack_is_u8, int B, int T, int H, int W, int ks, float threshold, void *stream);
 
+/* ---- K18: the step's ground truth from the right view (az_gt_prep.hip) ------------------------------------
+ * replaces train.py:255-272 (three F.interpolate(mode="nearest"), .type(torch.int), apply_disparity_cu with its two
+ * synchronising sign checks and zero-filled result, the two compares and the product of the mask) and test.py:91-110
+ * (the same with fixed sizes, disparity and depth warped by one disparity map, the label resized) -- one launch.
+ * disp_r [N,1,Hin,Win] f32; extra [N,Ce,Hin,Win] f32 or NULL with Ce = 0: channels warped by the same winners
+ * (test.py:110, the right depth); keep [N,Ck,Hin,Win] f32 or NULL with Ck = 0: channels resized only (train.py:258 the
+ * left depth, test.py:97 the label).  Outputs, all fully written: disp_l [N,1,H,W], extra_l [N,Ce,H,W], keep_s [N,Ck,H,W]
+ * (each NULL exactly when its input is), mask [N,1,H,W] one byte per pixel or NULL; stats: two int32 words the CALLER
+ * ZEROES.
+ *   resize   source index = min((int)floorf(dst * scale), in - 1) per axis: ATen's legacy "nearest" (not "nearest-exact");
+ *            scale_h / scale_w are the floats ATen itself uses: 1 / scale_factor (recompute_scale_factor=False) or
+ *            in / out when a size is given.  H <= Hin, W <= Win: this entry point does not upsample (AZ_EUNSUPPORTED).
+ *   scatter  d = the resized right disparity at (n,y,j); shift = d truncated toward zero (.type(torch.int)); the pixel lands
+ *            at t = j + shift if t < W; the smallest j wins a collision (az_warp_scatter, sign > 0); the value written is
+ *            the float d itself, and the extra channels at the same j; destinations nothing reaches are 0.
+ *            ONLY THE NON-NEGATIVE DIRECTION EXISTS: a ground-truth disparity is never negative.  d is compared as a float
+ *            before it is converted: d >= W lands nowhere; d <= -1, NaN or +-inf lands nowhere and is counted in stats[0]
+ *            -- the reference's sign assertion as a counter (cf. K16); d in (-1, 0) truncates to 0 and lands in place.
+ *   mask     (lo < disp_l) & (disp_l < hi) (train.py:272); stats[1] += the number of such pixels (counted with or without
+ *            a mask pointer), one atomic per workgroup.
+ * A required pointer null, a channel count that disagrees with its pointers, a non-positive size or scale: AZ_EINVAL;
+ * W > 4096: AZ_EUNSUPPORTED (at W = 4096 the winner table of a workgroup's four rows is 64 KiB of LDS; with its 32 bytes of
+ * counters the workgroup needs 65 568 bytes, which gfx950's 160 KiB per workgroup allows). */
+int az_gt_from_right(float *disp_l, float *extra_l, float *keep_s, uint8_t *mask, int32_t *stats, const float *disp_r,
+                     const float *extra, const float *keep, int N, int Ce, int Ck, int Hin, int Win, int H, int W,
+                     float scale_h, float scale_w, float lo, float hi, void *stream);
+
+/* ---- K19: colour-coded error images (az_error_img.hip) ---------------------------------------------------
+ * replaces utils/util.py:185-244 depth_error_img / disp_error_img with their tables gen_error_colormap_depth / _disp
+ * (:143-182), called on the host by train.py:353-356 and test.py:244,260 -- for all B images, on the device.
+ * est, gt [B,H,W] f32; mask one byte per pixel; kind 0 = disparity, 1 = depth; out f32, fully written, layout 0 =
+ * [B,H,W,3] (what the reference function builds), 1 = [B,3,H,W] (what train.py:354-356 turns it into).
+ * Per pixel in float32 with IEEE division: e = |gt - est|; disparity: e = min(e / abs_thres, (e / gt) / rel_thres) where a
+ * NaN on either side gives NaN (np.minimum); depth: e = e / abs_thres; the colour is r, g, b / 255 of the one table row
+ * with lower <= e < upper; black where the mask is off or no row matches (NaN, +inf, a negative quotient).  Last, the
+ * legend: rows < 10, columns [20 i, 20 i + 20) take the colour of row i in every image, over masked pixels too, clipped
+ * by the image.  A null pointer, another kind or layout, a non-positive size: AZ_EINVAL. */
+int az_error_img(float *out, const float *est, const float *gt, const uint8_t *mask, int kind, float abs_thres,
+                 float rel_thres, int layout, int B, int H, int W, void *stream);
+
 /* ---- K10/K11: RAFT-Stereo 1-D correlation (secondary path) -----------------------
  * replaces nets/raft/corr.py:115-161 (CorrBlock1D: einsum all-pairs correlation /
  * sqrt(C), avg_pool pyramid over the last axis, 2r+1-tap linear lookup through

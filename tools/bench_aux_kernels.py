@@ -8,7 +8,16 @@ runs the RAFT-Stereo prediction head instead (K15 convex upsampling + K16 sequen
 backward at mask [4,144,136,240]) beside the reference's arithmetic in PyTorch eager, and prints one JSON record.
 
     python tools/bench_aux_kernels.py temporal_ir [out.json]
-runs the temporal IR pattern (K17) at B=8, T=7, 540x960, ks=11 for uint8 and float32 stacks and prints one JSON record."""
+runs the temporal IR pattern (K17) at B=8, T=7, 540x960, ks=11 for uint8 and float32 stacks and prints one JSON record.
+
+    python tools/bench_aux_kernels.py gt_prep [out.json]
+    python tools/bench_aux_kernels.py error_img [out.json]
+time the step's ground-truth preparation (K18, B=4, 1080x1920 -> 540x960) against the operator chain of train.py:255-272, and
+the error image (K19, 540x960) against the numpy restatement fed from device tensors; one JSON record each (with an output
+path the record is merged into that file under its case name).  The chain of `gt_prep` runs through this library's own
+apply_disparity_cu (the K1 scatter kernel): the reference's extension does not exist on this platform.  `error_img` takes its
+numpy baseline and its input generator from the test infrastructure (tests/_gt_prep_ref.py, the restatement of
+utils/util.py:185-244): a recorded measurement, not a product path."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -176,6 +185,164 @@ def temporal_ir(out_path=None):
             fh.write(json.dumps(rec, indent=1) + "\n")
 
 
+def _write_case(rec, out_path):
+    """print the record; merge it into out_path under its case name"""
+    import json
+    print(json.dumps(rec))
+    if out_path:
+        doc = {}
+        if os.path.exists(out_path):
+            with open(out_path) as fh:
+                doc = json.load(fh)
+        doc[rec["case"]] = rec
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(doc, indent=1) + "\n")
+
+
+def gt_prep(out_path=None):
+    import statistics
+    import time
+    import torch.nn.functional as F
+    import bench as _bench
+    from activezero_amd import ops
+    from activezero_amd.utils.warp_ops import apply_disparity_cu
+    dev = torch.device("cuda:0")
+    B, Hin, Win, H, W, sets, reps, MAX_DISP = 4, 1080, 1920, 540, 960, 8, 20, 192
+    g = torch.Generator(device=dev).manual_seed(0)
+    # smooth disparity of 8..120 pixels with fractional parts, depth from it: 8 sets of 66 MB, more than the 256 MiB cache
+    disps, depths = [], []
+    for _ in range(sets):
+        coarse = 8 + 112 * torch.rand(B, 1, 9, 16, device=dev, generator=g)
+        d = F.interpolate(coarse, (Hin, Win), mode="bilinear", align_corners=False).contiguous()
+        disps.append(d)
+        depths.append((446.31 * 0.055 / d).contiguous())
+    half = lambda t: F.interpolate(t, scale_factor=0.5, mode="nearest", recompute_scale_factor=False)  # noqa: E731
+
+    def chain(i, sign):
+        depth_gt = half(depths[i])
+        r = half(disps[i])
+        disp_gt_l = apply_disparity_cu(r, r.type(torch.int), sign)
+        return disp_gt_l, depth_gt, (disp_gt_l < MAX_DISP) * (disp_gt_l > 0)
+
+    def fused(i):
+        disp_gt_l, _, depth_gt, mask, _ = ops.gt_from_right(disps[i], keep=depths[i], lo=0.0, hi=float(MAX_DISP))
+        return disp_gt_l, depth_gt, mask
+
+    for a, b in zip(fused(0), chain(0, None)):
+        assert torch.equal(a, b)
+
+    def wall(fn):
+        """host wall time per call: `sets` calls back to back on rotated inputs, device drained at either end"""
+        for i in range(sets):
+            fn(i)
+        us = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(sets):
+                fn(i)
+            torch.cuda.synchronize()
+            us.append((time.perf_counter() - t0) / sets * 1e6)
+        return {"us_per_call": statistics.median(us), "min_us": min(us)}
+
+    rec = {"case": "gt_prep", "input": [B, 1, Hin, Win], "output": [B, 1, H, W],
+           "timing": "host wall time around %d calls on %d rotated input sets, device drained before and after, median of %d"
+                     % (sets, sets, reps),
+           "fused": dict(wall(fused), launches=2, host_syncs=0, launches_are="the memset of the two counters, the kernel"),
+           "chain_with_sign_check": dict(wall(lambda i: chain(i, None)), launches=11, host_syncs=1, launches_are=(
+               "3 nearest resizes, the int cast, disp >= 0, all(), its 1-byte copy to the host (the sync), the scatter kernel, "
+               "2 compares, their product; counted from the code")),
+           "chain_sign_given": dict(wall(lambda i: chain(i, 1)), launches=8, host_syncs=0)}
+    # the kernel alone on preallocated outputs
+    outs = [(torch.empty(B, 1, H, W, device=dev), torch.empty(B, 1, H, W, device=dev),
+             torch.empty(B, 1, H, W, dtype=torch.uint8, device=dev)) for _ in range(sets)]
+    stats = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def launch(i):
+        ops._call("az_gt_from_right", outs[i][0].data_ptr(), None, outs[i][1].data_ptr(), outs[i][2].data_ptr(), stats.data_ptr(),
+                  disps[i].data_ptr(), None, depths[i].data_ptr(), B, 0, 1, Hin, Win, H, W, 2.0, 2.0, 0.0, float(MAX_DISP),
+                  ops._stream())
+
+    for _ in range(2):
+        for i in range(sets):
+            launch(i)
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(sets):
+            launch(i)
+        b.record(); torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b) / sets)
+    m = statistics.median(ms)
+    # touched: every 64-byte line of the 540 selected rows of both sources (stride-2 dwords), 4 + 4 + 1 bytes written per pixel
+    nbytes = float(B) * H * (2 * Win * 4) + float(B) * H * W * 9
+    probe = _bench.hbm_probe(dev)["GB/s"]
+    rec["kernel"] = {"ms": m, "min_ms": min(ms), "touched_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6, "copy_probe_GB/s": probe,
+                     "of_copy_probe": nbytes / m / 1e6 / probe,
+                     "bytes_are": "whole lines of the selected source rows (half of each is used) + disp_l, depth, mask written"}
+    rec["speedup_vs_chain_with_sign_check"] = rec["chain_with_sign_check"]["us_per_call"] / rec["fused"]["us_per_call"]
+    rec["speedup_vs_chain_sign_given"] = rec["chain_sign_given"]["us_per_call"] / rec["fused"]["us_per_call"]
+    _write_case(rec, out_path)
+
+
+def error_img(out_path=None):
+    import statistics
+    import time
+    import numpy as np
+    from activezero_amd import ops
+    from activezero_amd.utils.error_images import disp_error_img, disp_error_img_tensor
+    from tests import _gt_prep_ref as ref
+    dev = torch.device("cuda:0")
+    H, W, reps = 540, 960, 20
+    est, gt, mask = (torch.tensor(x, device=dev)[None] for x in ref.error_case(0, 1, H, W, "disp"))  # [1,1,H,W], as train.py:353
+
+    def host():  # utils/util.py:214-244 as train.py:353 runs it: three device-to-host copies, the numpy passes
+        e, g, m = (t.squeeze(0).detach().cpu().numpy() for t in (est, gt, mask))
+        return ref.error_img(e, g, m, "disp")[0]
+
+    def ours():
+        return disp_error_img(est, gt, mask)
+
+    assert np.array_equal(host(), ours())
+
+    def wall(fn):
+        for _ in range(3):
+            fn()
+        us = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            us.append((time.perf_counter() - t0) * 1e6)
+        return {"us_per_call": statistics.median(us), "min_us": min(us)}
+
+    rec = {"case": "error_img", "image": [1, H, W], "timing": "host wall time per call, device drained before and after, median of %d" % reps,
+           "drop_in_kernel_plus_one_copy": dict(wall(ours), host_syncs=1, bytes_to_host=12 * H * W),
+           "numpy_restatement_from_device_tensors": dict(wall(host), host_syncs=3, bytes_to_host=9 * H * W),
+           "tensor_variant_no_copy": dict(wall(lambda: disp_error_img_tensor(est, gt, mask)), host_syncs=0)}
+    e3, g3, m3 = est[0], gt[0], mask[0].view(torch.uint8)
+    out = torch.empty(1, 3, H, W, device=dev)
+    ms = []
+    for k in range(reps + 2):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(8):
+            ops._call("az_error_img", out.data_ptr(), e3.data_ptr(), g3.data_ptr(), m3.data_ptr(), 0, 3.0, 0.05, 1, 1, H, W, ops._stream())
+        b.record(); torch.cuda.synchronize()
+        if k >= 2:
+            ms.append(a.elapsed_time(b) / 8)
+    rec["kernel"] = {"ms": statistics.median(ms), "algorithmic_MB": 21.0 * H * W / 1e6, "GB/s": 21.0 * H * W / statistics.median(ms) / 1e6,
+                     "note": "8 launches on one 11 MB buffer set per event pair: cache-resident, launch-bound at this size"}
+    rec["speedup_drop_in_vs_numpy"] = (rec["numpy_restatement_from_device_tensors"]["us_per_call"]
+                                       / rec["drop_in_kernel_plus_one_copy"]["us_per_call"])
+    _write_case(rec, out_path)
+
+
+if len(sys.argv) > 1 and sys.argv[1] in ("gt_prep", "error_img"):
+    {"gt_prep": gt_prep, "error_img": error_img}[sys.argv[1]](sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "temporal_ir":
     temporal_ir(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)

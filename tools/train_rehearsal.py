@@ -13,26 +13,24 @@ import os
 import sys
 
 import torch
-import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from activezero_amd.datasets.messytable_synthetic import SyntheticMessytableDataset  # noqa: E402
 from activezero_amd.nets.psmnet.psmnet_3 import PSMNet  # noqa: E402
 from activezero_amd.utils import disp_losses  # noqa: E402
+from activezero_amd.utils.error_images import disp_error_img_tensor  # noqa: E402
+from activezero_amd.utils.gt_prep import prepare_sim_gt  # noqa: E402
 from activezero_amd.utils.reprojection import get_reproj_error_patch  # noqa: E402
-from activezero_amd.utils.warp_ops import apply_disparity_cu  # noqa: E402
 
 MAX_DISP, PATCH = 192, 11  # configs/config.py:12, 41
+IMG_OUTPUTS = {}  # the last step's train.py:357-363 images (what the TensorBoard writer would get)
 
 
 def train_sample(sample, model, opt):
     """train.py:237-312 (sim) and :369-419 (real)"""
     model.train()
     img_L, img_R = sample["img_sim_L"], sample["img_sim_R"]
-    half = lambda t: F.interpolate(t, scale_factor=0.5, mode="nearest", recompute_scale_factor=False)
-    img_disp_r = half(sample["img_disp_R"])                                   # :261-265
-    disp_gt_l = apply_disparity_cu(img_disp_r, img_disp_r.type(torch.int))    # :266-268
-    mask = (disp_gt_l < MAX_DISP) * (disp_gt_l > 0)                           # :272
+    disp_gt_l, _, mask = prepare_sim_gt(sample, MAX_DISP)                     # :248-272, one launch
     opt.zero_grad()
     out = model(img_L, img_R)
     sim_loss = disp_losses.psmnet_disp(out, disp_gt_l, mask)                  # losses.py:162-183
@@ -40,6 +38,8 @@ def train_sample(sample, model, opt):
     sim_loss = sim_loss + reproj                                              # losses.py:95-97
     sim_loss.backward()
     opt.step()
+    pred_disp = out[0].detach()
+    IMG_OUTPUTS["disp_err"] = disp_error_img_tensor(pred_disp[[0]], disp_gt_l[[0]], mask[[0]])  # :353-356, no host copy
     opt.zero_grad()
     out = model(sample["img_real_L"], sample["img_real_R"])
     real_loss, _, _ = get_reproj_error_patch(sample["img_real_L_reproj"], sample["img_real_R_reproj"], out[0], None, PATCH)
