@@ -94,6 +94,21 @@ ARITHS = ("f16x3", "bf16x6", "fp32")
 #   wgrad  one kd per wave                        0.42   0.52         0.29   0.38       0.42   0.23
 # Check (a) peaks at 0.40 (s2r16 mask 0 and the one-kd f16x3 weight gradient, a tap of one coarse position); the production-size
 # weight gradients (K = 195 840) stay below 0.001 in (b) and 0.03 in (c).
+#
+# The 1-D correlation GEMM of az_corr1d.hip (tests/test_gpu_corr_fp64.py through tests/_corr_fp64ref.py: bf16x6 only, the fp32
+# `* 1 / sqrt(C)` of its epilogue granted as a zero addend) uses the same constants; largest err / bound of checks (a) / (b) / (c)
+# measured on an MI355X per contraction and route (<A_KFAST,B_KFAST> instantiation, staging of the k-fast operands), over seeded
+# operands, per-channel powers of two 2^-8 .. 2^8 on one operand and an all-zero row / column:
+#                                               (a)    (b)    (c)
+#   volume  <F,F> (strided b32 staging)         0.36   0.64   0.66   ((3, 16, 70, 20, 20): K = 16, one block)
+#   d fmap1 <T,T> 16-byte staging               0.26   0.64   0.60   ((3, 16, 70, 20, 20): K = 20)
+#   d fmap1 <T,T> b32 staging                   0.17   0.40   0.32   ((1, 37, 2, 36, 31): K = 31)
+#   d fmap1 <F,F> (W2 = 1)                      0.05   0.08   0.10
+#   d fmap2 <F,T> 16-byte staging               0.18   0.45   0.56   ((3, 16, 70, 20, 20): K = 20)
+#   d fmap2 <F,T> b32 staging                   0.20   0.41   0.40   ((1, 3, 1, 2, 5): K = 2)
+#   d fmap2 <F,F> (H W1 = 1)                    0.07   0.15   0.19
+# The maxima again sit at the smallest K with many outputs; the model's C = 256 volume stays below 0.14 in (b) and (c), and the
+# 16-byte K tails beyond k = 64 ((1, 24, 2, 68, 100): K = 100 and 68) below 0.24.
 C = {
     "f16x3": 2.0,   # measured max 1.17 (wide weight gradient, 64 -> 32, (1, 1, 3, 3))
     "bf16x6": 3.0,  # measured max 1.51 (r16 AR 0 weight gradient, 64 -> 64, (1, 1, 3, 3))
