@@ -2,7 +2,9 @@
 The reference computes them with numpy / cv2 inside DataLoader workers, one image at a time; here a whole
 batch is processed on the device by az_ir_pattern (csrc/az_ir_pattern.hip).  get_temporal_ir_pattern is the twin of the
 reference's offline tool tools/temporal_ir.py (csrc/az_temporal_ir.hip): the pattern of a real view from its stack of
-projector exposures, made per item on the device instead of by a pass over the dataset before training."""
+projector exposures, made per item on the device instead of by a pass over the dataset before training.
+augment_images / data_augmentation are the twin of data_augmentation (dataset_utils.py:49-83: GaussianBlur, ColorJitter,
+ToTensor, Normalize) on az_augment (csrc/az_augment.hip): a batch of grey images in, normalised 3-channel images out."""
 import torch
 
 from activezero_amd import _lib
@@ -78,3 +80,94 @@ def get_smoothed_ir_pattern2(img_ir, img, ks=11, threshold=0.005):
     with torch.cuda.device(a.device):
         _call("az_ir_pattern", _p(out), _p(ws), ws_bytes, _p(a), _p(b_), n, h, w, int(ks), float(threshold), _stream())
     return out[0] if squeeze else out.view(img_ir.shape)
+
+
+def _column(value, n, name, device):
+    """one parameter of augment_images as n float32 values on the device, without a host round trip"""
+    if isinstance(value, torch.Tensor):
+        if value.device != device:
+            raise RuntimeError(f"{name}: must live on the device of grey ({device}), got {value.device}")
+        if value.numel() != n:
+            raise RuntimeError(f"{name}: expected {n} values (one per image), got {value.numel()}")
+        return value.reshape(n).to(torch.float32)
+    return torch.full((n,), float(value), dtype=torch.float32, device=device)
+
+
+def augment_images(grey, sigma=None, brightness=None, contrast=None, contrast_first=None, kernel_size=9):
+    """The transform dataset_utils.py:49-83 builds, for [H,W] or [B,H,W] grey CUDA images (float32 in [0,1], or uint8
+    levels taken as v / 255) -> [3,H,W] or [B,3,H,W] float32: GaussianBlur(kernel_size, sigma), ColorJitter with the fixed
+    factors `brightness` and `contrast` in the order `contrast_first` says (torchvision draws it per call), then the
+    ImageNet normalisation.  Each parameter is None (stage off), a number, or a CUDA tensor of B values; brightness and
+    contrast come together (the reference only ever enables both).  With every stage off the result is bit for bit
+    (grey - mean) / std.  sigma <= 0 leaves an image unblurred, factors are not range-checked (a device-side value cannot
+    raise without a synchronisation), NaN propagates."""
+    if not isinstance(grey, torch.Tensor):
+        raise TypeError("grey: expected a tensor")
+    if grey.dim() not in (2, 3):
+        raise RuntimeError("grey must be [H,W] or [B,H,W]")
+    if grey.dtype not in (torch.float32, torch.uint8):
+        raise RuntimeError(f"grey: expected torch.float32 or torch.uint8, got {grey.dtype}")
+    if (brightness is None) != (contrast is None):
+        raise RuntimeError("brightness and contrast are given together or not at all")
+    if contrast_first is not None and brightness is None:
+        raise RuntimeError("contrast_first needs brightness and contrast")
+    g = _chk((grey[None] if grey.dim() == 2 else grey).contiguous(), "grey", grey.dtype)
+    n, h, w = g.shape
+    flags = int(sigma is not None) | 2 * int(brightness is not None)
+    params = None
+    if flags:
+        one = lambda v, name: _column(0.0 if v is None else v, n, name, g.device)  # noqa: E731
+        params = torch.stack([one(sigma, "sigma"), one(brightness, "brightness"), one(contrast, "contrast"),
+                              one(contrast_first, "contrast_first")], dim=1).contiguous()
+    ws_bytes = _lib.lib().az_augment_workspace(n, h, w, int(kernel_size))
+    _lib.check(min(ws_bytes, 0), "az_augment_workspace")  # kernel_size or the image size out of range: nothing is launched
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=g.device)
+    out = torch.empty(n, 3, h, w, dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        _call("az_augment", _p(out), _p(ws), ws_bytes, _p(g), int(g.dtype == torch.uint8), _p(params), n, h, w,
+              int(kernel_size), flags, _stream())
+    return out[0] if grey.dim() == 2 else out
+
+
+class _Augmentation:
+    """what data_augmentation returns: the drawn parameters (sigma, brightness, contrast: [items] float32 on the device, or
+    None for a stage that is off) and the call that applies them"""
+
+    def __init__(self, sigma, brightness, contrast, kernel_size, generator, device):
+        self.sigma, self.brightness, self.contrast = sigma, brightness, contrast
+        self.kernel_size, self.generator, self.device = kernel_size, generator, device
+        self.last_order = None
+
+    def draw_order(self, n):
+        """n orders, 1 = contrast first: torchvision's ColorJitter permutes its adjustments at every application"""
+        return (torch.rand(n, generator=self.generator, device=self.device) < 0.5).to(torch.float32)
+
+    def __call__(self, grey):
+        if not isinstance(grey, torch.Tensor) or grey.dim() not in (3, 4):
+            raise RuntimeError("grey must be [B,H,W] or [B,V,H,W] (V views of B items)")
+        b, v = grey.shape[0], (grey.shape[1] if grey.dim() == 4 else 1)
+        items = next((p.numel() for p in (self.sigma, self.brightness) if p is not None), 1)
+        if items not in (1, b):
+            raise RuntimeError(f"parameters were drawn for {items} items, got {b}")
+        # the views of an item share its parameters (messytable.py:264-270); one drawn set serves any number of items
+        each = lambda p: None if p is None else p.expand(b)[:, None].expand(b, v).reshape(-1)  # noqa: E731
+        order = None
+        if self.brightness is not None:
+            order = self.last_order = self.draw_order(b * v)
+        out = augment_images(grey.reshape(b * v, *grey.shape[-2:]), each(self.sigma), each(self.brightness),
+                             each(self.contrast), order, self.kernel_size)
+        return out if grey.dim() == 3 else out.view(b, v, 3, *grey.shape[-2:])
+
+
+def data_augmentation(gaussian_blur=False, color_jitter=False, *, kernel_size=9, sigma=(0.1, 2.0), brightness=(0.4, 1.4),
+                      contrast=(0.8, 1.2), generator=None, items=1):
+    """dataset_utils.py:49-83 with the values of configs/config.py:104-113 as defaults.  Like the reference it draws the
+    parameters WHEN IT IS CALLED -- one (sigma, brightness, contrast) per item, uniform in the given ranges, with
+    torch.rand(items, 3, generator=generator) on the generator's device (the current CUDA device without one) -- and returns
+    a callable for [B,H,W] grey images, or [B,V,H,W] for V views per item which share the item's parameters; B = items, or
+    any B when items = 1.  The jitter order is drawn anew, per image, at each application.  Nothing synchronises."""
+    device = generator.device if generator is not None else torch.device("cuda", torch.cuda.current_device())
+    u = torch.rand(items, 3, generator=generator, device=device)
+    draw = lambda k, rng: rng[0] + (rng[1] - rng[0]) * u[:, k]  # noqa: E731
+    return _Augmentation(draw(0, sigma) if gaussian_blur else None, draw(1, brightness) if color_jitter else None,
+                         draw(2, contrast) if color_jitter else None, int(kernel_size), generator, device)

@@ -14,6 +14,10 @@ runs end to end without the dataset:
                                              back by messytable.py:406-426): per view a stack of 7 projector exposures
                                              [7,H,W] uint8 is rendered -- exposure k = texture + (k/6) dot gain + sensor
                                              noise, quantised to 0..255 -- and passed through get_temporal_ir_pattern
+  (augment=True) img_sim_L / img_sim_R go through the reference's data_augmentation with both of its switches on
+                                             (messytable.py:264-270: one drawn sigma, brightness and contrast for both
+                                             views; configs/config.py:104-113), on the device; the real images keep the
+                                             normalisation only (messytable.py:402-404)
 
 Geometry: a smooth random depth field -> disparity = focal * baseline / depth; the right view is the left one
 moved by the (integer-rounded) disparity with the scatter warp K1, so disparity, images and patterns are
@@ -21,7 +25,8 @@ mutually consistent and the losses have signal."""
 import torch
 import torch.nn.functional as F
 
-from activezero_amd.datasets.dataset_utils_gpu import get_smoothed_ir_pattern2, get_temporal_ir_pattern
+from activezero_amd.datasets.dataset_utils_gpu import (data_augmentation, get_smoothed_ir_pattern2,
+                                                       get_temporal_ir_pattern)
 from activezero_amd.utils.warp_ops import apply_disparity_cu
 
 _MEAN = (0.485, 0.456, 0.406)
@@ -30,8 +35,8 @@ _STD = (0.229, 0.224, 0.225)
 
 class SyntheticMessytableDataset(torch.utils.data.Dataset):
     def __init__(self, length=64, height=256, width=512, onReal=True, device="cuda:0", seed=0, max_disp=192,
-                 temporal=False):
-        self.temporal = bool(temporal)
+                 temporal=False, augment=False):
+        self.temporal, self.augment = bool(temporal), bool(augment)
         self.length, self.h, self.w, self.onReal = int(length), int(height), int(width), bool(onReal)
         self.device, self.seed, self.max_disp = torch.device(device), int(seed), int(max_disp)
         self.focal_length, self.baseline = 446.31, 0.055  # the order of the MessyTable rig (metres, half-res pixels)
@@ -89,6 +94,16 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
         g, _, _, rl0, rr0, lit = self._real_views(idx)
         return self._exposures(g, lit, torch.stack([rl0, rr0]))
 
+    def _augmentation(self, idx):
+        return data_augmentation(True, True, generator=self._gen(idx, 3))
+
+    def augmentation_params(self, idx):
+        """what item `idx` is augmented with (augment=True): sigma, brightness, contrast (one value each, shared by the two
+        views) and contrast_first [2] (left, right); for tests"""
+        aug = self._augmentation(idx)
+        return {"sigma": aug.sigma, "brightness": aug.brightness, "contrast": aug.contrast,
+                "contrast_first": aug.draw_order(2)}
+
     def __getitem__(self, idx):
         g = self._gen(idx, 1)
         left, right, left0, right0, disp2, depth2, disp_r2, depth_r2 = self._views(g)
@@ -102,6 +117,9 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
             "focal_length": torch.full((1, 1, 1), self.focal_length, device=self.device),
             "baseline": torch.full((1, 1, 1), self.baseline, device=self.device),
         }
+        if self.augment:
+            pair = self._augmentation(idx)(torch.stack([left, right])[None])[0]
+            item["img_sim_L"], item["img_sim_R"] = pair[0].contiguous(), pair[1].contiguous()
         if self.onReal:
             g, rl, rr, rl0, rr0, lit = self._real_views(idx)
             if self.temporal:

@@ -602,6 +602,31 @@ int az_gt_from_right(float *disp_l, float *extra_l, float *keep_s, uint8_t *mask
 int az_error_img(float *out, const float *est, const float *gt, const uint8_t *mask, int kind, float abs_thres,
                  float rel_thres, int layout, int B, int H, int W, void *stream);
 
+/* ---- K20: the loader's blur, colour jitter and normalisation (data side; az_augment.hip) -----
+ * replaces datasets/dataset_utils.py:49-83 data_augmentation as datasets/messytable.py:264-280, 402-404 applies it: for a
+ * grey image x in [0,1] whose three channels are equal until the last stage
+ *   blur      (flags bit 0) GaussianBlur: taps k = exp(-0.5 (t / sigma)^2), t = -(ks-1)/2 .. (ks-1)/2, k /= sum k, the 2-D
+ *             kernel outer(k, k), borders padded by ks / 2 with "reflect" (the edge pixel is not repeated); the taps are
+ *             formed in fp64 and rounded to fp32 once, the two 1-D passes accumulate in fp32
+ *   jitter    (flags bit 1) ColorJitter with fixed factors, in the order the caller drew: brightness clamp(b x, 0, 1) and
+ *             contrast clamp(c x + (1 - c) m, 0, 1), m = the mean over the image, as it stands when contrast runs, of
+ *             0.2989 x + 0.587 x + 0.114 x (the weights sum to 0.9999)
+ *   normalise out[ch] = (x - mean[ch]) / std[ch], ImageNet constants, a correctly rounded fp32 division: with both flags
+ *             clear the output is bit for bit torch's fp32 (x - mean) / std
+ * img: [B,H,W] grey, f32 in [0,1] or (img_is_u8 != 0) uint8 levels, taken as v / 255 (the bits of the f32 image u8 / 255);
+ * out: [B,3,H,W] f32; params: [B,4] f32 ON THE DEVICE, one row (sigma, brightness, contrast, order) per image, order 0 =
+ * brightness first, non-zero = contrast first; the columns of a stage whose flag is clear are ignored and params may be
+ * NULL when both are clear.  workspace of az_augment_workspace() bytes: one partial sum of m per 64 x 32 tile, added in a
+ * fixed order -- the result is the same bits from run to run and whatever B is.
+ * Device-side parameters cannot raise without a synchronisation, so they have a meaning instead: sigma <= 0 gives the
+ * unblurred image (the limit of the kernel); a negative factor is clamped like any other value; NaN propagates.
+ * A null pointer (but for params as above), B <= 0, flags outside 0..3: AZ_EINVAL; ks not odd or outside [3, 31]:
+ * AZ_EUNSUPPORTED; H or W <= ks / 2 (one reflection per border, torch's own condition): AZ_EINVAL, whatever the flags; a
+ * short workspace: AZ_EWORKSPACE; all before any launch, and the workspace query returns the same codes. */
+long long az_augment_workspace(int B, int H, int W, int ks);
+int az_augment(float *out, float *workspace, long long workspace_bytes, const void *img, int img_is_u8,
+               const float *params, int B, int H, int W, int ks, int flags, void *stream);
+
 /* ---- K10/K11: RAFT-Stereo 1-D correlation (secondary path) -----------------------
  * replaces nets/raft/corr.py:115-161 (CorrBlock1D: einsum all-pairs correlation /
  * sqrt(C), avg_pool pyramid over the last axis, 2r+1-tap linear lookup through

@@ -17,7 +17,12 @@ the error image (K19, 540x960) against the numpy restatement fed from device ten
 path the record is merged into that file under its case name).  The chain of `gt_prep` runs through this library's own
 apply_disparity_cu (the K1 scatter kernel): the reference's extension does not exist on this platform.  `error_img` takes its
 numpy baseline and its input generator from the test infrastructure (tests/_gt_prep_ref.py, the restatement of
-utils/util.py:185-244): a recorded measurement, not a product path."""
+utils/util.py:185-244): a recorded measurement, not a product path.
+
+    python tools/bench_aux_kernels.py augment [out.json]
+times the loader's blur + colour jitter + normalisation (K20, both stages on, ks = 9) at B = 8, 540x960 and at the training
+crop 256x512, for uint8 and float32 images: the kernel pair, the copy probe moving the same algorithmic bytes, and the plain
+torch fp32 operator chain (reflect F.pad, F.conv2d with the 2-D kernel, the blends, the normalisation) on the same inputs."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -185,6 +190,86 @@ def temporal_ir(out_path=None):
             fh.write(json.dumps(rec, indent=1) + "\n")
 
 
+def augment(out_path=None):
+    import json
+    import statistics
+    import torch.nn.functional as F
+    import bench as _bench
+    from activezero_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    B, ks, reps = 8, 9, 20
+    g = torch.Generator(device=dev).manual_seed(0)
+    mean = torch.tensor((0.485, 0.456, 0.406), device=dev).view(1, 3, 1, 1)
+    std = torch.tensor((0.229, 0.224, 0.225), device=dev).view(1, 3, 1, 1)
+    rec = {"case": "augment", "batch": B, "ks": ks, "flags": "blur + jitter, brightness first in every image",
+           "timing": "one call per buffer set, the sets rotated (together more than the 256 MiB cache), per event pair; "
+                     "median of %d after two warm-up rounds" % reps}
+
+    def events(fn, sets):
+        for _ in range(2):
+            for i in range(sets):
+                fn(i)
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(sets):
+                fn(i)
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / sets)
+        return statistics.median(ms), min(ms)
+
+    probe = _bench.hbm_probe(dev)["GB/s"]
+    rec["copy_probe_GB/s"] = probe
+    for H, W in ((540, 960), (256, 512)):
+        ws_bytes = _lib.lib().az_augment_workspace(B, H, W, ks)
+        for name, dtype, size in (("u8", torch.uint8, 1), ("f32", torch.float32, 4)):
+            per_set = B * H * W * (size + 12)
+            sets = max(8, -(-300 * (1 << 20) // per_set))
+            level = [(255 * torch.rand(B, H, W, device=dev, generator=g)).round() for _ in range(sets)]
+            imgs = [(v.to(torch.uint8) if size == 1 else v / 255) for v in level]
+            del level
+            u = torch.rand(B, 3, device=dev, generator=g)
+            params = torch.stack([0.1 + 1.9 * u[:, 0], 0.4 + u[:, 1], 0.8 + 0.4 * u[:, 2], torch.zeros(B, device=dev)], 1).contiguous()
+            wss = [torch.empty(ws_bytes // 4, device=dev) for _ in range(sets)]
+            outs = [torch.empty(B, 3, H, W, device=dev) for _ in range(sets)]
+
+            def launch(i):
+                ops._call("az_augment", outs[i].data_ptr(), wss[i].data_ptr(), ws_bytes, imgs[i].data_ptr(), int(size == 1),
+                          params.data_ptr(), B, H, W, ks, 3, ops._stream())
+
+            t = torch.arange(ks, device=dev) - ks // 2
+            k1 = torch.exp(-0.5 * (t[None] / params[:, :1]) ** 2)
+            k1 = k1 / k1.sum(1, keepdim=True)
+            k2 = (k1[:, :, None] * k1[:, None, :])[:, None]  # [B,1,ks,ks]: one 2-D kernel per image, a grouped convolution
+            bright, contrast = params[:, 1].view(B, 1, 1), params[:, 2].view(B, 1, 1)
+
+            def chain(i):
+                x = imgs[i].float() / 255 if size == 1 else imgs[i]
+                x = F.conv2d(F.pad(x[None], (ks // 2,) * 4, mode="reflect"), k2, groups=B)[0]
+                x = (bright * x).clamp(0, 1)
+                m = (0.2989 * x + 0.587 * x + 0.114 * x).mean((1, 2), keepdim=True)
+                x = (contrast * x + (1 - contrast) * m).clamp(0, 1)
+                return (x[:, None] - mean) / std
+
+            launch(0)
+            worst = float((outs[0] - chain(0)).abs().max())
+            assert worst < 1e-4, worst  # the two compute the same thing (fp32 both; the tests hold the kernel to fp64)
+            m, lo = events(launch, sets)
+            cm, clo = events(chain, sets)
+            nbytes = float(B) * H * W * (2 * size + 12)  # the image read by both passes, three planes written
+            rec["%dx%d_%s" % (H, W, name)] = {
+                "ms": m, "min_ms": lo, "algorithmic_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6,
+                "copy_probe_ms_same_bytes": nbytes / probe / 1e6, "of_copy_probe": nbytes / m / 1e6 / probe,
+                "torch_chain_ms": cm, "torch_chain_min_ms": clo, "speedup_vs_torch_chain": cm / m,
+                "buffer_sets": sets, "max_abs_diff_vs_chain": worst}
+            del imgs, wss, outs
+    print(json.dumps(rec))
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(rec, indent=1) + "\n")
+
+
 def _write_case(rec, out_path):
     """print the record; merge it into out_path under its case name"""
     import json
@@ -342,6 +427,9 @@ def error_img(out_path=None):
 
 if len(sys.argv) > 1 and sys.argv[1] in ("gt_prep", "error_img"):
     {"gt_prep": gt_prep, "error_img": error_img}[sys.argv[1]](sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "augment":
+    augment(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "temporal_ir":
     temporal_ir(sys.argv[2] if len(sys.argv) > 2 else None)

@@ -6,8 +6,8 @@ reference's own train.py imports yacs / tensorboardX / torchvision, none of whic
 this script is the executable rehearsal of "drops into train.py": the same calls in the same order on the
 same item dictionary.
 
-    python tools/train_rehearsal.py --iters 4 --batch 2
-"""
+    python tools/train_rehearsal.py --iters 4 --batch 2 [--augment]
+--augment: the simulated images go through the reference's default augmentation (blur + colour jitter, K20)."""
 import argparse
 import os
 import sys
@@ -52,9 +52,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--augment", action="store_true", help="blur and colour-jitter the simulated images (dataset_utils.py:49-83)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    ds = SyntheticMessytableDataset(length=a.iters * a.batch, device=dev)
+    ds = SyntheticMessytableDataset(length=a.iters * a.batch, device=dev, augment=a.augment)
     loader = torch.utils.data.DataLoader(ds, batch_size=a.batch, shuffle=False, num_workers=0)
     torch.manual_seed(1)
     model = PSMNet(MAX_DISP).to(dev)
