@@ -22,7 +22,9 @@
 
 __device__ __forceinline__ float pr_linspace01(int i, int n) {
     const float step = 1.0f / (float)(n - 1);
-    return (i < n / 2) ? (step * (float)i) : (1.0f - step * (float)(n - 1 - i));
+    // the upper half is ONE fused multiply-add, as torch's CPU kernel computes it (and as the compiler contracted it: this
+    // function lies outside the contract(off) scope of its caller)
+    return (i < n / 2) ? (step * (float)i) : fmaf(-step, (float)(n - 1 - i), 1.0f);
 }
 
 struct PrGeom {

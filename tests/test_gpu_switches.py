@@ -91,6 +91,15 @@ S2_CASES = [
 ]
 
 
+# The reprojection sweep against fp64 (tests/test_gpu_reproj_fp64.py) with K8 on the per-pixel kernel: every K8 test (the
+# million-pixel case among them: tiled by default, the per-pixel kernel's grid-stride loop here) and that file's route-coverage
+# test, which asserts under the switch that every K8 case is per-pixel.
+REPROJ = "tests/test_gpu_reproj_fp64.py"
+REPROJ_CASES = [
+    ({"AZ_PATCH_TILED": "0"}, REPROJ, "k8 or every_route or largest_ratios"),
+]
+
+
 def _child(env, path, expr):
     cmd = [sys.executable, "-m", "pytest", path, "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"]
     if expr:
@@ -118,6 +127,11 @@ def test_conv2d_sweep_behind_switch(env, path, expr):
 
 @pytest.mark.parametrize("env,path,expr", S2_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in S2_CASES])
 def test_strided_sweep_behind_switch(env, path, expr):
+    _child(env, path, expr)
+
+
+@pytest.mark.parametrize("env,path,expr", REPROJ_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in REPROJ_CASES])
+def test_reprojection_sweep_behind_switch(env, path, expr):
     _child(env, path, expr)
 
 
