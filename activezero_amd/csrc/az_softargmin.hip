@@ -206,12 +206,21 @@ softargmin_bwd_kernel(float *__restrict__ glogits, const float *__restrict__ gou
     sa_axis(X, xbase, p.lx0, p.wx1);
     // softmax shift M, normaliser s and the prediction: read back when the forward saved them
     // (training), recomputed otherwise.  p_D = exp(u_D - M) / s below uses the hardware exp2
-    // (v_exp_f32, 1 ulp): gradients do not need expf's range reduction, the forward keeps it.
+    // (v_exp_f32, 1 ulp), as the forward pass does.
+    // A lane past the right edge of the image (4 w % 64 != 0) has no pixel and no statistics.  It still takes part in
+    // the shuffles and writes its LDS cells, so every term of it must be exactly zero: its shift is +inf, which makes
+    // each exp2(-inf) = 0 whatever its (clamped, finite) tile cells hold.  With a live pixel's shift instead -- it used
+    // to read the one of pixel (0, 0, 0) of batch 0 -- a cell more than 88.7 above that shift overflowed the exp2 and
+    // g * e = 0 * inf = NaN travelled through from_right into the last live quad, i.e. into grad_logits[..., w - 1].
     float M, s, pred;
     if (stats) {
-        const size_t pix = live ? ((size_t)b * H + Y) * W + X : 0;
-        const float2 ms = stats[pix];
-        M = ms.x; s = ms.y; pred = fwd_out[pix];
+        if (live) {
+            const size_t pix = ((size_t)b * H + Y) * W + X;
+            const float2 ms = stats[pix];
+            M = ms.x; s = ms.y; pred = fwd_out[pix];
+        } else {
+            M = INFINITY; s = 1.f; pred = 0.f;
+        }
     } else {
         float t;
         sa_stats(tile, d, p, M, s, t);
