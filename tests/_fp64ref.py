@@ -109,6 +109,9 @@ ARITHS = ("f16x3", "bf16x6", "fp32")
 #   d fmap2 <F,F> (H W1 = 1)                    0.07   0.15   0.19
 # The maxima again sit at the smallest K with many outputs; the model's C = 256 volume stays below 0.14 in (b) and (c), and the
 # 16-byte K tails beyond k = 64 ((1, 24, 2, 68, 100): K = 100 and 68) below 0.24.
+#
+# The one-part arithmetics of the ConvGRU update (bf16x1, f16x1: tests/test_gpu_gru_fp64.py) have their own constants, bounds and
+# table of measured maxima in tests/_gru_fp64ref.py.
 C = {
     "f16x3": 2.0,   # measured max 1.17 (wide weight gradient, 64 -> 32, (1, 1, 3, 3))
     "bf16x6": 3.0,  # measured max 1.51 (r16 AR 0 weight gradient, 64 -> 64, (1, 1, 3, 3))
