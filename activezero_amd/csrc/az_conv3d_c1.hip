@@ -17,6 +17,7 @@
 //           (6 tile values per row: one ds_read_b128 + one ds_read_b64), 108 register
 //           accumulators per lane, LDS reduction per block, 864 float atomics per block.
 #include "az_common.h"
+#include "az_launch_math.h"
 
 #define C1_TH 8
 #define C1_TW 32
@@ -333,16 +334,7 @@ extern "C" int az_conv3d_c1_fwd(float *logits, const float *in, const float *w,
     if ((in_scale == nullptr) != (in_shift == nullptr)) return AZ_EINVAL;
     if (int e = c1_check(B, D, H, W)) return e;
     const int tiles_x = (W + C1F_TW - 1) / C1F_TW, tiles_y = (H + C1F_TH - 1) / C1F_TH;
-    // depth segment per block: every segment stages 2 halo planes, and the grid should fill a whole
-    // number of residency rounds (3 blocks per CU x 256 CUs by registers); minimise rounds x planes
-    int best = 1;
-    long long best_cost = -1;
-    for (int nseg = 1; nseg <= D; ++nseg) {
-        const int dseg = (D + nseg - 1) / nseg;
-        const long long blocks = (long long)tiles_x * tiles_y * B * ((D + dseg - 1) / dseg);
-        const long long cost = ((blocks + 767) / 768) * (dseg + 2);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = dseg; }
-    }
+    const int best = az_c1_fwd_dseg((long long)tiles_x * tiles_y * B, D);  // depth segment per block (az_launch_math.h: swept on the CPU)
     hipLaunchKernelGGL(c1_fwd_kernel, dim3(tiles_x * tiles_y, (D + best - 1) / best, B), dim3(256), 0,
                        az_stream(stream), logits, in, w, addend, in_scale, in_shift, D, H, W, tiles_x, best);
     return az_launch_status();
@@ -367,9 +359,23 @@ extern "C" int az_conv3d_c1_wgrad(float *grad_w, const float *in, const float *g
     if (hipMemsetAsync(grad_w, 0, 864 * sizeof(float), az_stream(stream)) != hipSuccess)
         return AZ_ELAUNCH;
     const int tiles_x = (W + C1_TW - 1) / C1_TW, tiles_y = (H + C1_TH - 1) / C1_TH;
-    const long long ntiles = (long long)B * D * tiles_y * tiles_x;
-    const unsigned grid = (unsigned)(ntiles < 2048 ? ntiles : 2048);
+    const long long ntiles = az_c1_wgrad_tiles(B, D, H, W);
+    const unsigned grid = (unsigned)az_c1_wgrad_grid(ntiles);  // (az_launch_math.h: swept on the CPU)
     hipLaunchKernelGGL(c1_wgrad_kernel, dim3(grid), dim3(256), 0, az_stream(stream), grad_w, in,
                        grad_logits, in_scale, in_shift, D, H, W, tiles_x, tiles_y, ntiles);
     return az_launch_status();
+}
+
+/* the launch plan of the three kernels for a shape, from the functions the launches call (az_launch_math.h) */
+extern "C" int az_conv3d_c1_plan(long long *plan, int B, int D, int H, int W) {
+    AZ_REQUIRE_PTR(plan);
+    if (int e = c1_check(B, D, H, W)) return e;
+    const long long patches = (long long)((W + C1F_TW - 1) / C1F_TW) * ((H + C1F_TH - 1) / C1F_TH) * B;
+    const int dseg = az_c1_fwd_dseg(patches, D);
+    const long long ntiles = az_c1_wgrad_tiles(B, D, H, W);
+    plan[0] = dseg;
+    plan[1] = patches * ((D + dseg - 1) / dseg);
+    plan[2] = ntiles;
+    plan[3] = az_c1_wgrad_grid(ntiles);
+    return AZ_OK;
 }

@@ -85,6 +85,34 @@ inline void az_c2r_segments(long long patches, int N, int &nseg, int &seg_len) {
     }
 }
 
+// az_conv3d_c1.hip, forward: depth segment per workgroup.  Every segment stages 2 halo planes, and the grid should fill a
+// whole number of residency rounds (3 workgroups per CU x 256 CUs by registers): the dseg = ceil(D / n) that minimises
+// rounds x (dseg + 2), the longest one among equals.  patches = B * 8-row patch rows * 16-voxel patch columns.
+// Postconditions: 1 <= dseg <= D; the nseg = ceil(D / dseg) segments have (nseg - 1) * dseg < D.
+#define AZ_C1_FWD_SLOTS 768
+inline long long az_c1_fwd_cost(long long patches, int D, int dseg) {
+    const long long blocks = patches * ((D + dseg - 1) / dseg);
+    return ((blocks + AZ_C1_FWD_SLOTS - 1) / AZ_C1_FWD_SLOTS) * (dseg + 2);
+}
+inline int az_c1_fwd_dseg(long long patches, int D) {
+    int best = 1;
+    long long best_cost = -1;
+    for (int nseg = 1; nseg <= D; ++nseg) {
+        const int dseg = (D + nseg - 1) / nseg;
+        const long long cost = az_c1_fwd_cost(patches, D, dseg);
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = dseg; }
+    }
+    return best;
+}
+// az_conv3d_c1.hip, weight gradient: workgroup g of `grid` walks the (batch, plane, 8 x 32 tile) items g, g + grid, ...
+#define AZ_C1_WGRAD_MAX_GRID 2048
+inline long long az_c1_wgrad_tiles(int B, int D, int H, int W) {
+    return (long long)B * D * ((H + 7) / 8) * ((W + 31) / 32);
+}
+inline int az_c1_wgrad_grid(long long ntiles) {
+    return (int)(ntiles < AZ_C1_WGRAD_MAX_GRID ? ntiles : AZ_C1_WGRAD_MAX_GRID);
+}
+
 // linear index -> (patch column, 8-row patch row, depth segment, batch) of az_conv3d_roll.hip
 AZ_HD void az_roll_decode(int lin, int tiles_x, int tyb, int nseg, int &tix, int &tiy, int &seg, int &b) {
     tix = lin % tiles_x; lin /= tiles_x;

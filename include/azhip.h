@@ -334,6 +334,11 @@ int az_conv3d_c1_dgrad(float *grad_in, const float *grad_logits, const float *w,
                        int H, int W, void *stream);
 int az_conv3d_c1_wgrad(float *grad_w, const float *in, const float *grad_logits, const float *in_scale,
                        const float *in_shift, int B, int D, int H, int W, void *stream);
+/* The launch plan of the three for a shape, computed by the functions the launches themselves call; the refusals of the
+ * launches (a dimension <= 0: AZ_EINVAL; B or D above 65535: AZ_EUNSUPPORTED).  plan[0] = planes per depth segment of a
+ * forward workgroup, [1] = forward workgroups (8 x 16 patches x depth segments x B), [2] = (batch, plane, 8 x 32 tile)
+ * items of the weight gradient, [3] = its workgroups: workgroup g takes items g, g + plan[3], ... */
+int az_conv3d_c1_plan(long long *plan /* [4] */, int B, int D, int H, int W);
 
 /* ---- BatchNorm3d pieces around K4/K5 (psmnet_submodule_3.py:55) --------------------
  * finalize: merge the conv partials (Chan, fp64) -> mean, invstd, scale = gamma*invstd,

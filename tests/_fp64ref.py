@@ -112,6 +112,9 @@ ARITHS = ("f16x3", "bf16x6", "fp32")
 #
 # The one-part arithmetics of the ConvGRU update (bf16x1, f16x1: tests/test_gpu_gru_fp64.py) have their own constants, bounds and
 # table of measured maxima in tests/_gru_fp64ref.py.
+#
+# The 32 -> 1 classifier convolutions of az_conv3d_c1.hip (VALU, fp32: tests/test_gpu_c1_fp64.py) use the fp32 constants with a
+# rounding count of their own for check (a); their table of measured maxima is in tests/_c1_fp64ref.py.
 C = {
     "f16x3": 2.0,   # measured max 1.17 (wide weight gradient, 64 -> 32, (1, 1, 3, 3))
     "bf16x6": 3.0,  # measured max 1.51 (r16 AR 0 weight gradient, 64 -> 64, (1, 1, 3, 3))

@@ -258,6 +258,67 @@ int main() {
                     }
         }
     }
+    // 9. the 32 -> 1 classifier convolutions (az_conv3d_c1.hip).  Forward: the depth segments tile [0, D) -- every plane is
+    //    written by exactly one workgroup of a patch -- and no segment length has a lower cost.  Weight gradient: the strided
+    //    walk of at most 2048 workgroups visits every (batch, plane, tile) item exactly once and decodes it inside the volume
+    {
+        const long long patch_counts[] = {1, 2, 3, 7, 30, 48, 100, 255, 256, 257, 383, 384, 385, 767, 768, 769, 1000, 1536, 2040, 3000, 4080, 6528};
+        for (int D = 1; D <= 2100; ++D)
+            for (long long patches : patch_counts) {
+                const int dseg = az_c1_fwd_dseg(patches, D);
+                CHECK(dseg >= 1 && dseg <= D, "c1 patches %lld D %d: dseg %d", patches, D, dseg);
+                if (dseg < 1) continue;
+                const int nseg = (D + dseg - 1) / dseg;
+                CHECK((long long)nseg * dseg >= D && (long long)(nseg - 1) * dseg < D, "c1 D %d: %d segments of %d", D, nseg, dseg);
+                std::vector<char> written((size_t)D, 0);
+                for (int seg = 0; seg < nseg; ++seg) {  // the kernel's d0, d1 of blockIdx.y = seg
+                    const int d0 = seg * dseg, d1 = d0 + dseg < D ? d0 + dseg : D;
+                    CHECK(d0 < d1, "c1 D %d dseg %d: empty segment %d", D, dseg, seg);
+                    for (int od = d0; od < d1; ++od) { CHECK(!written[(size_t)od], "c1 plane %d twice", od); written[(size_t)od] = 1; }
+                }
+                for (int od = 0; od < D; ++od) CHECK(written[(size_t)od], "c1 D %d dseg %d: plane %d never written", D, dseg, od);
+                const long long cost = az_c1_fwd_cost(patches, D, dseg);
+                for (int other = 1; other <= D; ++other) {
+                    const long long c = az_c1_fwd_cost(patches, D, other);
+                    CHECK(c >= cost, "c1 patches %lld D %d: dseg %d costs %lld, %d costs %lld", patches, D, dseg, cost, other, c);
+                    if (c == cost && (D + other - 1) / other != nseg) CHECK(other < dseg, "c1 D %d: the longer equal %d not taken", D, other);
+                }
+            }
+        // (values the launches had before the selection moved here)
+        CHECK(az_c1_fwd_dseg(17LL * 15, 48) == 16 && az_c1_fwd_dseg(3LL * 5 * 9, 7) == 2 && az_c1_fwd_dseg(8LL * 10, 20) == 3 &&
+              az_c1_fwd_dseg(1, 2050) == 3 && az_c1_fwd_dseg(768, 3) == 3 && az_c1_fwd_dseg(2LL * 15, 48) == 2 &&
+              az_c1_fwd_dseg(3LL * 2 * 5, 5) == 1, "c1 forward segment lengths changed");
+        const int shapes[][4] = {{1, 1, 1, 1}, {1, 2050, 3, 5}, {768, 3, 8, 16}, {1, 48, 16, 240}, {3, 7, 40, 130}, {2, 5, 7, 13}, {1, 48, 136, 240},
+                                 {5, 9, 17, 65}, {1, 2047, 8, 32}, {1, 2048, 8, 32}, {1, 2049, 9, 33}, {3, 1367, 1, 1}, {65535, 1, 1, 1}};
+        for (const auto &sh : shapes) {
+            const int B = sh[0], D = sh[1], H = sh[2], W = sh[3];
+            const int tiles_x = (W + 31) / 32, tiles_y = (H + 7) / 8;
+            const long long ntiles = az_c1_wgrad_tiles(B, D, H, W);
+            const int grid = az_c1_wgrad_grid(ntiles);
+            CHECK(ntiles == (long long)B * D * tiles_y * tiles_x, "c1 wgrad tiles %lld", ntiles);
+            CHECK(grid >= 1 && grid <= AZ_C1_WGRAD_MAX_GRID && grid <= ntiles && (grid == ntiles || grid == AZ_C1_WGRAD_MAX_GRID),
+                  "c1 wgrad grid %d of %lld tiles", grid, ntiles);
+            std::vector<char> seen((size_t)ntiles, 0);
+            for (int blk = 0; blk < grid; ++blk)
+                for (long long item = blk; item < ntiles; item += grid) {
+                    CHECK(!seen[(size_t)item], "c1 wgrad item %lld twice", item);
+                    seen[(size_t)item] = 1;
+                    long long r = item;  // the kernel's decode
+                    const int tx0 = (int)(r % tiles_x) * 32; r /= tiles_x;
+                    const int ty0 = (int)(r % tiles_y) * 8; r /= tiles_y;
+                    const int od = (int)(r % D), b = (int)(r / D);
+                    CHECK(tx0 < W && ty0 < H && od >= 0 && od < D && b >= 0 && b < B, "c1 wgrad item %lld -> (%d, %d, %d, %d)", item, b, od, ty0, tx0);
+                }
+            for (long long i = 0; i < ntiles; ++i) CHECK(seen[(size_t)i], "c1 wgrad item %lld never visited", i);
+        }
+        for (long long nt = 1; nt <= 5000; ++nt) {
+            const int grid = az_c1_wgrad_grid(nt);
+            CHECK(grid == (nt < 2048 ? nt : 2048), "c1 wgrad grid %d of %lld", grid, nt);
+            long long visited = 0;
+            for (int blk = 0; blk < grid; ++blk) visited += (nt - blk + grid - 1) / grid;
+            CHECK(visited == nt, "c1 wgrad: %lld of %lld items visited", visited, nt);
+        }
+    }
     std::printf("launch math: %d failures\n", fails);
     return fails ? 1 : 0;
 }
