@@ -12,7 +12,7 @@
 
 __global__ void __launch_bounds__(256)
 cost_volume_fwd_ncdhw(float *__restrict__ cost, const float *__restrict__ fl,
-                      const float *__restrict__ fr, int C, int d, int h, int w) {
+                      const float *__restrict__ fr, int C, int d, int h, int w, int vec) {
     extern __shared__ float row[];
     // blockIdx.x = (b * 2C + c2) * h + y
     const int y = blockIdx.x % h;
@@ -25,7 +25,7 @@ cost_volume_fwd_ncdhw(float *__restrict__ cost, const float *__restrict__ fl,
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float *out = cost + ((size_t)bc * d * h + y) * w;  // plane i adds i*h*w
     const size_t plane = (size_t)h * w;
-    if ((w & 3) == 0) {
+    if (vec) {  // w % 4 == 0 and cost 16-byte aligned: so is every output row
         const int w4 = w >> 2;
         for (int i = wave; i < d; i += 4) {
             float4 *o4 = reinterpret_cast<float4 *>(out + i * plane);
@@ -141,6 +141,10 @@ static int check_dims(int B, int C, int d, int h, int w) {
     return AZ_OK;
 }
 
+static bool aligned16(const void *a, const void *b, const void *c) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
+
 extern "C" int az_cost_volume_fwd(float *cost, const float *fl, const float *fr, int B, int C,
                                   int d, int h, int w, void *stream) {
     AZ_REQUIRE_PTR(cost); AZ_REQUIRE_PTR(fl); AZ_REQUIRE_PTR(fr);
@@ -148,8 +152,10 @@ extern "C" int az_cost_volume_fwd(float *cost, const float *fl, const float *fr,
     if ((size_t)w * sizeof(float) > 64 * 1024) return AZ_EUNSUPPORTED;
     const long long blocks = (long long)B * 2 * C * h;
     if (blocks > 0x7fffffffLL) return AZ_EUNSUPPORTED;
+    // NCDHW promises no alignment: the float4 stores need w % 4 == 0 AND an aligned cost, else the scalar path
+    const int vec = (w % 4 == 0 && aligned16(cost, nullptr, nullptr)) ? 1 : 0;
     hipLaunchKernelGGL(cost_volume_fwd_ncdhw, dim3((unsigned)blocks), dim3(256),
-                       (size_t)w * sizeof(float), az_stream(stream), cost, fl, fr, C, d, h, w);
+                       (size_t)w * sizeof(float), az_stream(stream), cost, fl, fr, C, d, h, w, vec);
     return az_launch_status();
 }
 
@@ -168,6 +174,7 @@ extern "C" int az_cost_volume_fwd_ndhwc(float *cost, const float *fl, const floa
     AZ_REQUIRE_PTR(cost); AZ_REQUIRE_PTR(fl); AZ_REQUIRE_PTR(fr);
     if (int e = check_dims(B, C, d, h, w)) return e;
     if (C % 4) return AZ_EUNSUPPORTED;
+    if (!aligned16(cost, fl, fr)) return AZ_EINVAL;  // float4 lanes
     const long long rows = (long long)B * d * h;
     hipLaunchKernelGGL(cost_volume_fwd_ndhwc, dim3((unsigned)(rows < 8192 ? rows : 8192)), dim3(256), 0,
                        az_stream(stream), reinterpret_cast<float4 *>(cost),
@@ -181,6 +188,7 @@ extern "C" int az_cost_volume_bwd_ndhwc(float *gl, float *gr, const float *g, in
     AZ_REQUIRE_PTR(gl); AZ_REQUIRE_PTR(gr); AZ_REQUIRE_PTR(g);
     if (int e = check_dims(B, C, d, h, w)) return e;
     if (C % 4) return AZ_EUNSUPPORTED;
+    if (!aligned16(gl, gr, g)) return AZ_EINVAL;  // float4 lanes
     const long long total4 = (long long)B * h * w * (2 * C / 4);
     hipLaunchKernelGGL(cost_volume_bwd_ndhwc, dim3(az_grid_for(total4, 256)), dim3(256), 0,
                        az_stream(stream), reinterpret_cast<float4 *>(gl),

@@ -139,6 +139,8 @@ extern "C" int az_costconv_assemble_fwd(float *out, const float *F_bulk, const f
                                         int D, int H, int W, void *stream) {
     AZ_REQUIRE_PTR(out); AZ_REQUIRE_PTR(F_bulk); AZ_REQUIRE_PTR(F_edge); AZ_REQUIRE_PTR(G);
     AZ_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0);
+    AZ_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(F_bulk) | reinterpret_cast<uintptr_t>(F_edge) |
+                 reinterpret_cast<uintptr_t>(G)) & 15) == 0);  // float4 lanes
     const long long total = (long long)B * D * H * W * 8;
     hipLaunchKernelGGL(costconv_assemble_fwd_kernel, dim3(az_grid_for(total, 256)), dim3(256), 0, az_stream(stream),
                        (float4 *)out, (const float4 *)F_bulk, (const float4 *)F_edge, (const float4 *)G, D, H, W,
@@ -150,6 +152,8 @@ extern "C" int az_costconv_assemble_bwd(float *dF_bulk, float *dF_edge, float *d
                                         int D, int H, int W, void *stream) {
     AZ_REQUIRE_PTR(dF_bulk); AZ_REQUIRE_PTR(dF_edge); AZ_REQUIRE_PTR(dG); AZ_REQUIRE_PTR(grad_out);
     AZ_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0);
+    AZ_REQUIRE(((reinterpret_cast<uintptr_t>(dF_bulk) | reinterpret_cast<uintptr_t>(dF_edge) | reinterpret_cast<uintptr_t>(dG) |
+                 reinterpret_cast<uintptr_t>(grad_out)) & 15) == 0);  // float4 lanes
     const long long tf = (long long)B * H * W * 8, tg = (long long)B * H * (W + 2) * 8;
     hipLaunchKernelGGL(costconv_grad_f_kernel, dim3(az_grid_for(tf, 256)), dim3(256), 0, az_stream(stream),
                        (float4 *)dF_bulk, (float4 *)dF_edge, (const float4 *)grad_out, D, H, W,

@@ -17,7 +17,11 @@ struct SppArgs {
     float sy, sx;       // (in - 1) / (out - 1), 0 for out == 1
 };
 
+// The position is ROUNDED to fp32 before the index is subtracted (ATen's recipe): contracted into fma(scale, dst, -i0) --
+// as the compiler did in the backward kernels only -- l1 keeps the bits the forward's src lost, by up to half an ulp of src,
+// and the backward is no longer the adjoint of the forward.
 __device__ __forceinline__ void spp_src(float scale, int dst, int n_in, int &i0, int &ip, float &l0, float &l1) {
+#pragma clang fp contract(off)
     const float src = scale * (float)dst;
     i0 = min((int)src, n_in - 1);
     ip = i0 < n_in - 1 ? 1 : 0;

@@ -61,14 +61,17 @@ int az_warp_scatter(float *dst, const float *src, const int32_t *disp, int N, in
  * replaces nets/psmnet/psmnet_3.py:149-163 (nets/psmnet/psmnet.py:151-165).
  * feat_l, feat_r: [B,C,h,w]; cost: [B,2C,d,h,w] (NCDHW).
  *   cost[b,c,i,y,x]   = feat_l[b,c,y,x]      (x >= i) else 0
- *   cost[b,C+c,i,y,x] = feat_r[b,c,y,x-i]    (x >= i) else 0            */
+ *   cost[b,C+c,i,y,x] = feat_r[b,c,y,x-i]    (x >= i) else 0
+ * No pointer alignment is required beyond a float's: 16-byte stores are used
+ * only when w % 4 == 0 and cost is 16-byte aligned.                        */
 int az_cost_volume_fwd(float *cost, const float *feat_l, const float *feat_r, int B, int C,
                        int d, int h, int w, void *stream);
 /* adjoint: grad_l[b,c,y,x] = sum_{i<=x} g[b,c,i,y,x];
  *          grad_r[b,c,y,x] = sum_{i, x+i<w} g[b,C+c,i,y,x+i]              */
 int az_cost_volume_bwd(float *grad_l, float *grad_r, const float *grad_cost, int B, int C,
                        int d, int h, int w, void *stream);
-/* channels-last twins: feat_*: [B,h,w,C], cost: [B,d,h,w,2C] */
+/* channels-last twins: feat_*: [B,h,w,C], cost: [B,d,h,w,2C]; C % 4 == 0, else
+ * AZ_EUNSUPPORTED; every pointer 16-byte aligned, else AZ_EINVAL */
 int az_cost_volume_fwd_ndhwc(float *cost, const float *feat_l, const float *feat_r, int B,
                              int C, int d, int h, int w, void *stream);
 int az_cost_volume_bwd_ndhwc(float *grad_l, float *grad_r, const float *grad_cost, int B,
@@ -728,7 +731,8 @@ int az_seq_loss_bwd(float *g_pred, const float *pred, const float *gt, const voi
  * for x - d >= -2, else 0.  The backward writes the matching reductions of grad_out over d. */
 int az_costconv_edge_width(int D, int W); /* XE = min(W, D+1): columns on which the delta < 2 maps exist */
 int az_costconv_num_classes(int D);       /* NC = min(D, 3) depth classes: first / middle / last plane */
-/* F_bulk [B,H,W,NC*32] (x - d >= 2, per depth class), F_edge [B,H,XE,NC*128] (x - d = -2..1), G [B,H,W+2,NC*64] */
+/* F_bulk [B,H,W,NC*32] (x - d >= 2, per depth class), F_edge [B,H,XE,NC*128] (x - d = -2..1), G [B,H,W+2,NC*64];
+ * every pointer of the two assemble calls 16-byte aligned, else AZ_EINVAL */
 /* the merged kernels themselves (costconv.py: 0/1-masked sums of the [32][64][3][3][3] weight over kd, and over kw into the
  * shifted column for K_R): kl [ncls][5][32][32][3][3], kr [ncls][2][32][32][3][5]; ml [ncls][5][3][3], mr [ncls][2][3][3][5];
  * _bwd: the adjoint, grad_weight fully written */
