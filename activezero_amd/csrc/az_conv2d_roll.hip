@@ -21,7 +21,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "az_roll_common.h"
+#include "az_roll_epilogue.h"
 #include "az_launch_math.h"
 
 struct C2RArgs {
@@ -157,12 +157,12 @@ conv2d_roll_kernel(const C2RArgs a) {
     };
     const float floor_ = a.relu ? 0.f : -__builtin_inff();
 
-    // BatchNorm partials: see az_conv3d_roll.hip -- element e = 4 m + r of a lane (its x offset in the quarter) is valid
-    // iff e < st_nv; two channels per lane (N tiles 0, 1)
+    // BatchNorm partials (az_roll_epilogue.h): element e = 4 m + r of a lane (its x offset in the quarter) is valid
+    // iff e < st_nv; one channel per lane and N tile
     const int oh_l = ty0 + 4 * wr + (lane >> 4);
     int st_nv = 0;
     if (EPI == 1) st_nv = (oh_l < a.H) ? min(max(a.W - (tx0 + 8 * wc), 0), 8) : 0;
-    float st_k[NT], st_s1[NT], st_s2[NT];
+    float st_k[NT], st_s1[NT], st_s2[NT];  // (not a RollSums: as one aggregate hipcc spills 18 registers at NT = 4)
 #pragma unroll
     for (int n = 0; n < NT; ++n) { st_k[n] = 0.f; st_s1[n] = 0.f; st_s2[n] = 0.f; }
     int st_planes = 0;
@@ -187,14 +187,8 @@ conv2d_roll_kernel(const C2RArgs a) {
                 const f32x4 v = r16_quad_transpose(acc[m][n], lane);
                 const bool vok = row_ok && ow < a.W;
                 const unsigned off = vok ? (pix_row + (unsigned)ow) * (unsigned)(a.out_cs * 4) + (unsigned)(ch0 + 16 * n + cq) * 4u : R_OOB;
-                float4 y = make_float4(v[0] * sc.x + sf.x, v[1] * sc.y + sf.y, v[2] * sc.z + sf.z, v[3] * sc.w + sf.w);
-                if (EPI == 2) {
-                    const unsigned roff = vok ? (pix_row + (unsigned)ow) * (unsigned)(a.res_cs * 4) + (unsigned)(ch0 + 16 * n + cq) * 4u : R_OOB;
-                    const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, roff, 0, 0));
-                    y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
-                }
-                if (EPI != 1) { y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_); }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
+                const unsigned roff = vok ? (pix_row + (unsigned)ow) * (unsigned)(a.res_cs * 4) + (unsigned)(ch0 + 16 * n + cq) * 4u : R_OOB;
+                az_roll_finish_piece<EPI == 2, EPI != 1>(az_roll_affine_mul(v, sc, sf), rs_res, roff, floor_, rs_out, off);
             }
         }
         if (EPI == 1) {
@@ -219,22 +213,9 @@ conv2d_roll_kernel(const C2RArgs a) {
         const unsigned row_id = (unsigned)(((seg * a.tiles_yb + tiy) * a.tiles_x + tix) * 4 + wv);
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            float cnt = (float)(st_nv * st_planes);
-            float mean = cnt > 0.f ? st_k[n] + st_s1[n] / cnt : 0.f;
-            float m2 = cnt > 0.f ? st_s2[n] - st_s1[n] * st_s1[n] / cnt : 0.f;
-#pragma unroll
-            for (int off = 16; off < 64; off <<= 1) {
-                const float n_o = __shfl_xor(cnt, off), mean_o = __shfl_xor(mean, off), m2_o = __shfl_xor(m2, off);
-                const float nn = cnt + n_o;
-                const float dlt = mean_o - mean;
-                const float w_o = nn > 0.f ? n_o / nn : 0.f;
-                m2 = m2 + m2_o + dlt * dlt * cnt * w_o;
-                mean = mean + dlt * w_o;
-                cnt = nn;
-            }
             const unsigned ch = (unsigned)(ch0 + 16 * n + (lane & 15));
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(cnt * mean, fmaxf(m2, 0.f))), rs_part,
-                                                  lane < 16 ? (unsigned)((((size_t)g * a.cout + ch) * a.rows + row_id) * 8) : R_OOB, 0, 0);
+            const float cnt = az_roll_flush_channel<16, 64>(st_k[n], st_s1[n], st_s2[n], (float)(st_nv * st_planes), rs_part,
+                                                            lane < 16 ? (unsigned)((((size_t)g * a.cout + ch) * a.rows + row_id) * 8) : R_OOB);
             if (n == 0)
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, cnt), rs_cnt,
                                                       (lane == 0 && cg == 0) ? (unsigned)(((size_t)g * a.rows + row_id) * 4) : R_OOB, 0, 0);
@@ -437,11 +418,7 @@ conv2d_roll64_kernel(const C2RArgs a) {
     const int oh_l = ty0 + 4 * wm + trow;
     const int cl = 32 * wn + 4 * (lane >> 4);
     const float floor_ = a.relu ? 0.f : -__builtin_inff();
-    float hk[2][4], hs1[2][4], hs2[2][4];
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { hk[n][r] = 0.f; hs1[n][r] = 0.f; hs2[n][r] = 0.f; }
+    RollSums<8> hst;  // (channel 4 n + r of the lane's two quads)
     int h_n = 0;
     bool h_first = true;
     auto finish = [&](int o, bool ok) __attribute__((always_inline)) {
@@ -451,37 +428,24 @@ conv2d_roll64_kernel(const C2RArgs a) {
 #pragma unroll
             for (int n = 0; n < 2; ++n)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) hk[n][r] = (ok && h_first) ? acc[n][0][r] * osc : hk[n][r];
+                for (int r = 0; r < 4; ++r) hst.k[4 * n + r] = (ok && h_first) ? acc[n][0][r] * osc : hst.k[4 * n + r];
             h_first = h_first && !ok;
         }
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sf = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (EPI != 1) {
-                if (a.scale) sc = *reinterpret_cast<const float4 *>(a.scale + cl + 16 * n);
-                if (a.shift) sf = *reinterpret_cast<const float4 *>(a.shift + cl + 16 * n);
-            }
+            float4 sc, sf;
+            az_roll_load_affine(EPI != 1, a.scale, a.shift, cl + 16 * n, sc, sf);
             sc.x *= osc; sc.y *= osc; sc.z *= osc; sc.w *= osc;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int ow = tx0 + 4 * m + tcol;
                 const bool vok = row_ok && ow < a.W;
                 const unsigned off = vok ? (pix_row + (unsigned)ow) * (unsigned)(a.out_cs * 4) + (unsigned)(cl + 16 * n) * 4u : R_OOB;
-                const f32x4 c = acc[n][m];
-                float4 y = make_float4(fmaf(c[0], sc.x, sf.x), fmaf(c[1], sc.y, sf.y), fmaf(c[2], sc.z, sf.z), fmaf(c[3], sc.w, sf.w));
-                if (EPI == 2) {
-                    const unsigned roff = vok ? (pix_row + (unsigned)ow) * (unsigned)(a.res_cs * 4) + (unsigned)(cl + 16 * n) * 4u : R_OOB;
-                    const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, roff, 0, 0));
-                    y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
-                }
-                if (EPI != 1) { y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_); }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
+                const unsigned roff = vok ? (pix_row + (unsigned)ow) * (unsigned)(a.res_cs * 4) + (unsigned)(cl + 16 * n) * 4u : R_OOB;
+                const float4 y = az_roll_finish_piece<EPI == 2, EPI != 1>(az_roll_affine_fma(acc[n][m], sc, sf), rs_res, roff, floor_, rs_out, off);
                 if (EPI == 1) {
                     if (n == 0) h_n += vok ? 1 : 0;
-                    const float d0_ = vok ? y.x - hk[n][0] : 0.f, d1_ = vok ? y.y - hk[n][1] : 0.f, d2_ = vok ? y.z - hk[n][2] : 0.f, d3_ = vok ? y.w - hk[n][3] : 0.f;
-                    hs1[n][0] += d0_; hs1[n][1] += d1_; hs1[n][2] += d2_; hs1[n][3] += d3_;
-                    hs2[n][0] = fmaf(d0_, d0_, hs2[n][0]); hs2[n][1] = fmaf(d1_, d1_, hs2[n][1]);
-                    hs2[n][2] = fmaf(d2_, d2_, hs2[n][2]); hs2[n][3] = fmaf(d3_, d3_, hs2[n][3]);
+                    hst.add_voxel(4 * n, y, vok);
                 }
             }
         }
@@ -494,24 +458,10 @@ conv2d_roll64_kernel(const C2RArgs a) {
         for (int n = 0; n < 2; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float cnt = (float)h_n;
-                float mean = cnt > 0.f ? hk[n][r] + hs1[n][r] / cnt : 0.f;
-                float m2 = cnt > 0.f ? hs2[n][r] - hs1[n][r] * hs1[n][r] / cnt : 0.f;
-#pragma unroll
-                for (int off = 1; off < 16; off <<= 1) {  // the 16 pixel lanes of this channel quad
-                    const float n_o = __shfl_xor(cnt, off), mean_o = __shfl_xor(mean, off), m2_o = __shfl_xor(m2, off);
-                    const float nn = cnt + n_o;
-                    const float dlt = mean_o - mean;
-                    const float w_o = nn > 0.f ? n_o / nn : 0.f;
-                    m2 = m2 + m2_o + dlt * dlt * cnt * w_o;
-                    mean = mean + dlt * w_o;
-                    cnt = nn;
-                }
-                ntot = cnt;
                 const unsigned ch = (unsigned)(cl + 16 * n + r);
                 const size_t rowp = ((size_t)g * a.cout + ch) * a.rows + row_base;
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(cnt * mean, fmaxf(m2, 0.f))), rs_part,
-                                                      (lane & 15) == 0 ? (unsigned)((rowp + wm) * 8) : R_OOB, 0, 0);
+                ntot = az_roll_flush_channel<1, 16>(hst.k[4 * n + r], hst.s1[4 * n + r], hst.s2[4 * n + r], (float)h_n, rs_part,
+                                                    (lane & 15) == 0 ? (unsigned)((rowp + wm) * 8) : R_OOB);
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(0.f, 0.f)), rs_part,
                                                       (lane & 15) == 0 ? (unsigned)((rowp + 2 + wm) * 8) : R_OOB, 0, 0);
             }

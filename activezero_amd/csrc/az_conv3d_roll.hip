@@ -35,7 +35,7 @@
 
 #include "az_conv3d_args.h"
 
-#include "az_roll_common.h"
+#include "az_roll_epilogue.h"
 #include "az_options.h"
 #include "az_launch_math.h"
 
@@ -194,12 +194,9 @@ conv3d_roll_kernel(const ConvArgs a) {
     };
     // per-channel epilogue constants, loaded once (four consecutive channels per lane after the quad transpose)
     const int cq = co0 + wn * 16 + (lane & 12);
-    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sf = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (EPI != 1) {
-        if (a.scale) sc = *reinterpret_cast<const float4 *>(a.scale + cq);
-        if (a.shift) sf = *reinterpret_cast<const float4 *>(a.shift + cq);
-        if (AR) { sc.x = ldexpf(sc.x, out_exp); sc.y = ldexpf(sc.y, out_exp); sc.z = ldexpf(sc.z, out_exp); sc.w = ldexpf(sc.w, out_exp); }
-    }
+    float4 sc, sf;
+    az_roll_load_affine(EPI != 1, a.scale, a.shift, cq, sc, sf);
+    if (AR && EPI != 1) az_roll_ldexp4(sc, out_exp);
     const float floor_ = a.relu ? 0.f : -__builtin_inff();
 
     // validity of the 16 accumulator elements of every lane for the BatchNorm partials -- the same for every depth: the
@@ -207,17 +204,9 @@ conv3d_roll_kernel(const ConvArgs a) {
     // i.e. e < st_nv with ONE per-lane count (sixteen 64-bit lane masks in SGPRs made hipcc spill scalars into the stage)
     int st_nv = 0;
     if (EPI == 1) st_nv = (ty0 + 4 * wm + (lane >> 4) < a.Ho) ? min(max(a.Wo - tx0, 0), 16) : 0;
-    // BatchNorm partials (EPI 1): ONE entry per channel for the wave's 4x16 half patch over the whole depth segment.
-    // Every lane keeps running sums of its 16 accumulator elements about a shift of its own (the first valid value
-    // it sees: shifted-data algorithm, no cancellation in sum-of-squares minus squared-sum) -- 64 VALU instructions per
-    // finished plane and no cross-lane traffic; lanes and row groups are merged once, after the walk (Chan's formula).
-    // The first version reduced every plane to a (sum, centred M2) entry of its own (~100 VALU and four cross-lane sums
-    // per plane, 9 spilled registers, 97 920 partial rows per V0 layer for the finalize kernels to merge; this form: no
-    // spills, 4 080 rows, no pre-merge launch).  Both cost nothing measurable in the kernel itself: 1.42 ms with or
-    // without statistics (profiles/r03_roll_kernel_notes.md section 6 -- the 0.2 ms "epilogue gap" quoted earlier was
-    // the timing script measuring this kernel first, before the clocks had settled).
-    const int st_nl = st_nv;  // this lane's valid elements per plane
-    float st_k = 0.f, st_s1 = 0.f, st_s2 = 0.f;
+    // BatchNorm partials (EPI 1, az_roll_epilogue.h): ONE entry per channel for the wave's 4x16 half patch over the whole
+    // depth segment; a lane's sums run over its 16 accumulator elements of every finished plane
+    RollSums<1> st;
     int st_planes = 0;
     bool st_first = true;
 
@@ -226,65 +215,32 @@ conv3d_roll_kernel(const ConvArgs a) {
         const int oh = ty0 + 4 * wm + (lane >> 4);  // row of the 4x4 tiles this lane's accumulator registers belong to
         const bool row_ok = ok && oh < a.Ho;
         const unsigned row_off = (unsigned)((o * a.Ho + oh) * a.Wo) * OVB + (unsigned)cq * 4u;
-        if (EPI != 1) {
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const int ow = tx0 + 4 * m + (lane & 3);
-                const f32x4 v = r16_quad_transpose(acc[2][m], lane);
-                const unsigned off = (row_ok && ow < a.Wo) ? row_off + (unsigned)ow * OVB : R_OOB;
-                float4 y = make_float4(v[0] * sc.x + sf.x, v[1] * sc.y + sf.y, v[2] * sc.z + sf.z, v[3] * sc.w + sf.w);
-                if (EPI == 2) {
-                    const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0));
-                    y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
-                }
-                y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
-            }
-        } else {
-            // raw output; BatchNorm running sums (see st_k above)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const f32x4 vt = r16_quad_transpose(acc[2][m], lane);
-                const int owt = tx0 + 4 * m + (lane & 3);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vt), rs_out,
-                                                       (row_ok && owt < a.Wo) ? row_off + (unsigned)owt * OVB : R_OOB, 0, 0);
-            }
-            st_k = (ok && st_first) ? acc[2][0][0] : st_k;  // (element (0,0) is valid whenever any of the lane's is)
+        for (int m = 0; m < 4; ++m) {
+            const int ow = tx0 + 4 * m + (lane & 3);
+            const f32x4 v = r16_quad_transpose(acc[2][m], lane);
+            const unsigned off = (row_ok && ow < a.Wo) ? row_off + (unsigned)ow * OVB : R_OOB;
+            const float4 y = EPI == 1 ? __builtin_bit_cast(float4, v) : az_roll_affine_mul(v, sc, sf);  // (EPI 1: raw output)
+            az_roll_finish_piece<EPI == 2, EPI != 1>(y, rs_res, off, floor_, rs_out, off);
+        }
+        if (EPI == 1) {
+            st.k[0] = (ok && st_first) ? acc[2][0][0] : st.k[0];  // (element (0,0) is valid whenever any of the lane's is)
             st_first = st_first && !ok;
             st_planes += ok ? 1 : 0;
             const int nv_p = ok ? st_nv : 0;
 #pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float dlt = (m * 4 + r < nv_p) ? acc[2][m][r] - st_k : 0.f;
-                    st_s1 += dlt;
-                    st_s2 = fmaf(dlt, dlt, st_s2);
-                }
+            for (int m = 0; m < 4; ++m) st.add_tile(0, acc[2][m], 4 * m, nv_p);
         }
     };
 
     // after the walk: merge the lanes of a channel (the four row groups of the 16x16 C layout) and write the entry
     auto flush_stats = [&]() {
-        float n = (float)(st_nl * st_planes);
-        float mean = n > 0.f ? st_k + st_s1 / n : 0.f;
-        float m2 = n > 0.f ? st_s2 - st_s1 * st_s1 / n : 0.f;
-#pragma unroll
-        for (int off = 16; off < 64; off <<= 1) {
-            const float n_o = __shfl_xor(n, off), mean_o = __shfl_xor(mean, off), m2_o = __shfl_xor(m2, off);
-            const float nn = n + n_o;
-            const float dlt = mean_o - mean;
-            const float w_o = nn > 0.f ? n_o / nn : 0.f;
-            m2 = m2 + m2_o + dlt * dlt * n * w_o;
-            mean = mean + dlt * w_o;
-            n = nn;
-        }
         const int tiy4 = 2 * tiy + wm;
         const bool tile_ok = tiy4 < a.tiles_y;
         const unsigned tile_id = (unsigned)(((b * a.nseg + seg) * a.tiles_y + tiy4) * a.tiles_x + tix);
         const unsigned ch = co0 + wn * 16 + (lane & 15);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(n * mean, fmaxf(m2, 0.f))), rs_part,
-                                              (tile_ok && lane < 16) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB, 0, 0);
+        const float n = az_roll_flush_channel<16, 64>(st.k[0], st.s1[0], st.s2[0], (float)(st_nv * st_planes), rs_part,
+                                                      (tile_ok && lane < 16) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, n), rs_cnt,
                                               (tile_ok && lane == 0 && wn == 0 && co0 == 0) ? tile_id * 4u : R_OOB, 0, 0);
     };
@@ -375,18 +331,12 @@ conv3d_roll_kernel(const ConvArgs a) {
     // four channels 16 wn + 4 (lane >> 4) + r: no transpose.  y = acc * 2^out_exp (+ residual); no affine map, no ReLU
     // (an input gradient has neither).
     const int cqh = co0 + wn * 16 + 4 * (lane >> 4);
-    float4 sch = make_float4(1.f, 1.f, 1.f, 1.f), sfh = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (AR) {
-        if (EPI != 1) {
-            if (a.scale) sch = *reinterpret_cast<const float4 *>(a.scale + cqh);
-            if (a.shift) sfh = *reinterpret_cast<const float4 *>(a.shift + cqh);
-        }
-        // the power-of-two unscaling rides on the affine map (out_exp beyond the float range: the true result is, too)
-        sch.x = ldexpf(sch.x, out_exp); sch.y = ldexpf(sch.y, out_exp); sch.z = ldexpf(sch.z, out_exp); sch.w = ldexpf(sch.w, out_exp);
-    }
-    // BatchNorm partials (EPI 1), this layout: per lane running sums of its FOUR channels over its voxel of each tile
-    // (shifted-data sums as in the bf16x6 form above); lanes of a channel quad are merged once, after the walk
-    float hk[4] = {0.f, 0.f, 0.f, 0.f}, hs1[4] = {0.f, 0.f, 0.f, 0.f}, hs2[4] = {0.f, 0.f, 0.f, 0.f};
+    float4 sch, sfh;
+    az_roll_load_affine(AR && EPI != 1, a.scale, a.shift, cqh, sch, sfh);
+    if (AR) az_roll_ldexp4(sch, out_exp);
+    // BatchNorm partials (EPI 1), this layout: per lane running sums of its FOUR channels over its voxel of each tile;
+    // the 16 voxel lanes of a channel quad are merged once, after the walk
+    RollSums<4> hst;
     int h_n = 0;
     bool h_first = true;
     auto finish_h = [&](int o, bool ok) {
@@ -395,7 +345,7 @@ conv3d_roll_kernel(const ConvArgs a) {
         const unsigned row_off = (unsigned)((o * a.Ho + oh) * a.Wo) * OVB + (unsigned)cqh * 4u;
         if (EPI == 1) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) hk[r] = (row_ok && h_first) ? acc[2][0][r] * sch.x : hk[r];  // (sch.x = 2^out_exp here)
+            for (int r = 0; r < 4; ++r) hst.k[r] = (row_ok && h_first) ? acc[2][0][r] * sch.x : hst.k[r];  // (sch.x = 2^out_exp here)
             h_first = h_first && !row_ok;
         }
 #pragma unroll
@@ -403,23 +353,12 @@ conv3d_roll_kernel(const ConvArgs a) {
             const int ow = tx0 + 4 * m + (lane & 3);
             const bool vok = row_ok && ow < a.Wo;
             const unsigned off = vok ? row_off + (unsigned)ow * OVB : R_OOB;
-            float4 y = make_float4(fmaf(acc[2][m][0], sch.x, sfh.x), fmaf(acc[2][m][1], sch.y, sfh.y),
-                                   fmaf(acc[2][m][2], sch.z, sfh.z), fmaf(acc[2][m][3], sch.w, sfh.w));
-            if (EPI == 2) {
-                const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0));
-                y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
-            }
-            if (EPI != 1) { y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_); }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
+            const float4 y = az_roll_finish_piece<EPI == 2, EPI != 1>(az_roll_affine_fma(acc[2][m], sch, sfh), rs_res, off, floor_, rs_out, off);
             if (EPI == 1) {
                 h_n += vok ? 1 : 0;
                 const float v[4] = {y.x, y.y, y.z, y.w};
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float dlt = vok ? v[r] - hk[r] : 0.f;
-                    hs1[r] += dlt;
-                    hs2[r] = fmaf(dlt, dlt, hs2[r]);
-                }
+                for (int r = 0; r < 4; ++r) hst.add(r, v[r], vok);
             }
         }
     };
@@ -430,23 +369,9 @@ conv3d_roll_kernel(const ConvArgs a) {
         float ntot = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            float n = (float)h_n;
-            float mean = n > 0.f ? hk[r] + hs1[r] / n : 0.f;
-            float m2 = n > 0.f ? hs2[r] - hs1[r] * hs1[r] / n : 0.f;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {  // the 16 voxel lanes of this channel quad
-                const float n_o = __shfl_xor(n, off), mean_o = __shfl_xor(mean, off), m2_o = __shfl_xor(m2, off);
-                const float nn = n + n_o;
-                const float dlt = mean_o - mean;
-                const float w_o = nn > 0.f ? n_o / nn : 0.f;
-                m2 = m2 + m2_o + dlt * dlt * n * w_o;
-                mean = mean + dlt * w_o;
-                n = nn;
-            }
-            ntot = n;
             const unsigned ch = (unsigned)(cqh + r);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(n * mean, fmaxf(m2, 0.f))), rs_part,
-                                                  (tile_ok && (lane & 15) == 0) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB, 0, 0);
+            ntot = az_roll_flush_channel<1, 16>(hst.k[r], hst.s1[r], hst.s2[r], (float)h_n, rs_part,
+                                                (tile_ok && (lane & 15) == 0) ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB);
         }
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ntot), rs_cnt,
                                               (tile_ok && lane == 0 && wn == 0 && co0 == 0) ? tile_id * 4u : R_OOB, 0, 0);

@@ -36,7 +36,7 @@
 #include <type_traits>
 
 #include "az_conv3d_args.h"
-#include "az_roll_common.h"
+#include "az_roll_epilogue.h"
 #include "az_options.h"
 #include "az_launch_math.h"
 
@@ -177,15 +177,12 @@ conv3d_s2roll_kernel(const ConvArgs a) {
 
     // epilogue constants: this lane's four channels 16 cg + 4 (lane >> 4) + r
     const int cqh = cg * 16 + 4 * (lane >> 4);
-    float4 sch = make_float4(1.f, 1.f, 1.f, 1.f), sfh = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (EPI == 0) {
-        if (a.scale) sch = *reinterpret_cast<const float4 *>(a.scale + cqh);
-        if (a.shift) sfh = *reinterpret_cast<const float4 *>(a.shift + cqh);
-    }
-    sch.x = ldexpf(sch.x, out_exp); sch.y = ldexpf(sch.y, out_exp); sch.z = ldexpf(sch.z, out_exp); sch.w = ldexpf(sch.w, out_exp);
+    float4 sch, sfh;
+    az_roll_load_affine(EPI == 0, a.scale, a.shift, cqh, sch, sfh);
+    az_roll_ldexp4(sch, out_exp);
     const float osc = ldexpf(1.f, out_exp);
     const float floor_ = (EPI == 0 && a.relu) ? 0.f : -__builtin_inff();
-    float hk[4] = {0.f, 0.f, 0.f, 0.f}, hs1[4] = {0.f, 0.f, 0.f, 0.f}, hs2[4] = {0.f, 0.f, 0.f, 0.f};
+    RollSums<4> hst;  // BatchNorm partials (EPI 1, az_roll_epilogue.h): this lane's four channels over its voxels
     int h_n = 0;
     bool h_first = true;
 
@@ -193,8 +190,8 @@ conv3d_s2roll_kernel(const ConvArgs a) {
     auto finish = [&](int t) __attribute__((always_inline)) {
         if (EPI == 1) {  // the shift of the running sums: the first value this lane sees (any value near the data serves)
             const f32x4 c = acc[0][0];
-            hk[0] = h_first ? c[0] * osc : hk[0]; hk[1] = h_first ? c[1] * osc : hk[1];
-            hk[2] = h_first ? c[2] * osc : hk[2]; hk[3] = h_first ? c[3] * osc : hk[3];
+            hst.k[0] = h_first ? c[0] * osc : hst.k[0]; hst.k[1] = h_first ? c[1] * osc : hst.k[1];
+            hst.k[2] = h_first ? c[2] * osc : hst.k[2]; hst.k[3] = h_first ? c[3] * osc : hst.k[3];
             h_first = false;
         }
 #pragma unroll
@@ -203,19 +200,12 @@ conv3d_s2roll_kernel(const ConvArgs a) {
             const bool vok = oy < a.Ho && ox < a.Wo;
             const unsigned off = vok ? (unsigned)((t * a.Ho + oy) * a.Wo + ox) * 256u + (unsigned)cqh * 4u : R_OOB;
             const f32x4 c = acc[0][m];
-            float4 y = EPI == 1 ? make_float4(c[0] * osc, c[1] * osc, c[2] * osc, c[3] * osc)
-                                : make_float4(fmaf(c[0], sch.x, sfh.x), fmaf(c[1], sch.y, sfh.y), fmaf(c[2], sch.z, sfh.z), fmaf(c[3], sch.w, sfh.w));
-            if (EPI == 0) {
-                const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, off, 0, 0));
-                y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
-                y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_);
-            }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
+            // (EPI 1: the scalar osc is the only scale)
+            const float4 y = az_roll_finish_piece<EPI == 0, EPI == 0>(
+                EPI == 1 ? make_float4(c[0] * osc, c[1] * osc, c[2] * osc, c[3] * osc) : az_roll_affine_fma(c, sch, sfh), rs_res, off, floor_, rs_out, off);
             if (EPI == 1) {
                 h_n += vok ? 1 : 0;
-                const float d0 = vok ? y.x - hk[0] : 0.f, d1 = vok ? y.y - hk[1] : 0.f, d2 = vok ? y.z - hk[2] : 0.f, d3 = vok ? y.w - hk[3] : 0.f;
-                hs1[0] += d0; hs1[1] += d1; hs1[2] += d2; hs1[3] += d3;
-                hs2[0] = fmaf(d0, d0, hs2[0]); hs2[1] = fmaf(d1, d1, hs2[1]); hs2[2] = fmaf(d2, d2, hs2[2]); hs2[3] = fmaf(d3, d3, hs2[3]);
+                hst.add_voxel(0, y, vok);
             }
         }
 #pragma unroll
@@ -325,23 +315,9 @@ conv3d_s2roll_kernel(const ConvArgs a) {
         float ntot = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            float n = (float)h_n;
-            float mean = n > 0.f ? hk[r] + hs1[r] / n : 0.f;
-            float m2 = n > 0.f ? hs2[r] - hs1[r] * hs1[r] / n : 0.f;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {  // the 16 voxel lanes of this channel quad
-                const float n_o = __shfl_xor(n, off), mean_o = __shfl_xor(mean, off), m2_o = __shfl_xor(m2, off);
-                const float nn = n + n_o;
-                const float dlt = mean_o - mean;
-                const float w_o = nn > 0.f ? n_o / nn : 0.f;
-                m2 = m2 + m2_o + dlt * dlt * n * w_o;
-                mean = mean + dlt * w_o;
-                n = nn;
-            }
-            ntot = n;
             const unsigned ch = (unsigned)(cqh + r);
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, make_float2(n * mean, fmaxf(m2, 0.f))), rs_part,
-                                                  (lane & 15) == 0 ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB, 0, 0);
+            ntot = az_roll_flush_channel<1, 16>(hst.k[r], hst.s1[r], hst.s2[r], (float)h_n, rs_part,  // (the 16 voxel lanes of this channel quad)
+                                                (lane & 15) == 0 ? (unsigned)(((size_t)ch * a.ntiles + tile_id) * 8) : R_OOB);
         }
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ntot), rs_cnt, (lane == 0 && cg == 0) ? tile_id * 4u : R_OOB, 0, 0);
     }

@@ -132,6 +132,13 @@ def test_every_route_of_the_family_is_swept():
     want += ["xcd"] if opt("AZ_WGRAD_R16_XCD") and opt("AZ_WGRAD_R16_WGS") % 8 == 0 else []
     missing = [n for n in want if not any(n in r for r in names)]
     assert not missing, (missing, sorted(names))
+    # the forward epilogues (affine + residual + ReLU, BatchNorm partials) run on every forward route
+    fwd = {route("fwd", ci, co, a, s) for (ci, co, s, a) in EPILOGUE}
+    want = ["roll f16x3", "gather f16x3", "gather fp32", "gather bf16x6"]
+    want += ["roll2 f16x3"] if opt("AZ_CONV_ROLL64") else []
+    want += ["roll bf16x6" if conv3d._ROLL else ("m128 bf16x6" if opt("AZ_CONV_M128") else "gather bf16x6")]
+    missing = [n for n in want if n not in fwd]
+    assert not missing, (missing, sorted(fwd))
 
 
 def run(kind, cin, cout, arith, x, wt, dy, residual=None):
@@ -224,6 +231,68 @@ def test_dgrad_residual_handover(cin, cout, shape, arith, capsys):
     r = R.check(got, arith, R.products("dgrad", dy, wt), ex, sref, R.amax_of(dy), R.amax_of(wt), addend=res)
     record(arith, "dgrad", f"dgrad+residual {cin}->{cout} {shape} {arith} [{name}]", r, capsys)
     assert max(r) <= 1.0, (name, r)
+
+
+# ---- the forward epilogues on every forward route --------------------------------------------------------------------------
+# one voxel (variance exactly 0, every other lane empty); ragged rows and columns with a second half patch that is partly
+# outside; batch 3 with three column tiles, the last one voxel wide; depth 13 with four patch rows and a dead last half.
+# Behind AZ_ROLL_SEGLEN=5 (tests/test_gpu_switches.py) depth 13 walks segments of 5, 5 and 3 planes and depth 5 one of five:
+# the state the rolling kernel carries from plane to plane.
+EPILOGUE = [(ci, co, s, a) for (ci, co) in PAIRS for s in [(1, 1, 1, 1), (1, 5, 7, 19), (3, 2, 5, 33), (1, 13, 25, 17)]
+            for a in R.ARITHS]
+EPILOGUE_IDS = [f"{ci}x{co}-{'x'.join(map(str, s))}-{a}" for (ci, co, s, a) in EPILOGUE]
+
+
+def _fwd_verdict(got, cin, cout, shape, arith, **kw):
+    x, wt, _ = operands(cin, cout, shape)
+    ex = reference("fwd", cin, cout, shape)
+    sref = R.split_reference("fwd", x, wt, arith)
+    return R.check(got, arith, R.products("fwd", x, wt), ex, sref, R.amax_of(x), R.amax_of(wt), **kw)
+
+
+@pytest.mark.parametrize("cin,cout,shape,arith", EPILOGUE, ids=EPILOGUE_IDS)
+def test_forward_affine_residual_relu_epilogue(cin, cout, shape, arith, capsys):
+    """relu(conv * scale + shift + res) in the kernel's epilogue"""
+    x, wt, dy = operands(cin, cout, shape)
+    sc, sh = seeded((cout,), 7440) * 0.5 + 1.0, seeded((cout,), 7441) * 0.3
+    sc[::5] *= -1.0
+    res = seeded(tuple(dy.shape), 7442) * 0.5
+    name = route("fwd", cin, cout, arith, shape)
+    with torch.no_grad():
+        got = ncdhw(conv3d._conv(cl(x), wt.to(DEV), conv3d.CONV_S1, PREC[arith], scale=sc.to(DEV), shift=sh.to(DEV),
+                                 residual=cl(res), relu=True))
+    r = _fwd_verdict(got, cin, cout, shape, arith, epilogue=(sc, sh, res, True))
+    record(arith, "fwd", f"epilogue {cin}->{cout} {shape} {arith} [{name}]", r, capsys)
+    assert max(r) <= 1.0, (name, r)
+    assert float(got.min()) >= 0.0
+
+
+@pytest.mark.parametrize("cin,cout,shape,arith", EPILOGUE, ids=EPILOGUE_IDS)
+def test_forward_batchnorm_partials(cin, cout, shape, arith, capsys):
+    """the BatchNorm-partials launch: its raw output through the three checks, its partials merged by Chan's rule (as
+    az_bn3d_finalize) to the moments of that output, every output voxel counted once"""
+    x, wt, _ = operands(cin, cout, shape)
+    name = route("fwd", cin, cout, arith, shape)
+    with torch.no_grad():
+        raw, part, cnt, ntiles = conv3d._conv(cl(x), wt.to(DEV), conv3d.CONV_S1, PREC[arith], stats=True)
+    r = _fwd_verdict(ncdhw(raw), cin, cout, shape, arith)
+    record(arith, "fwd", f"stats {cin}->{cout} {shape} {arith} [{name}]", r, capsys)
+    assert max(r) <= 1.0, (name, r)
+    part, cnt = part.double().cpu(), cnt.double().cpu()
+    assert tuple(part.shape) == (cout, ntiles, 2)
+    vox = raw.numel() // cout
+    assert float(cnt.sum()) == vox  # every output voxel counted once
+    y = raw.double().reshape(-1, cout).cpu()
+    mean = part[:, :, 0].sum(1) / vox
+    live = cnt > 0
+    tile_mean = torch.where(live, part[:, :, 0] / cnt.clamp_min(1.0), torch.zeros_like(part[:, :, 0]))
+    m2 = (part[:, :, 1] + cnt * (tile_mean - mean[:, None]) ** 2 * live).sum(1)
+    var = y.var(0, unbiased=False)
+    with capsys.disabled():  # error / allowance of the two moments (<= 1 passes)
+        print(f"  moments: mean {float(((mean - y.mean(0)).abs() / (1e-6 + 1e-5 * y.mean(0).abs())).max()):.4f}"
+              f" var {float(((m2 / vox - var).abs() / (1e-7 + 2e-4 * var.abs())).max()):.4f}")
+    torch.testing.assert_close(mean, y.mean(0), rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(m2 / vox, var, rtol=2e-4, atol=1e-7)
 
 
 # ---- pre-split operands (include/azhip.h "S2 format") ------------------------------------------------------------------------

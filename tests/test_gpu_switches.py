@@ -61,6 +61,8 @@ S1_CASES = [
     ({"AZ_CONV_ROLL": "0", "AZ_CONV_M128": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and bf16x6 and not wgrad or every_route"),
     ({"AZ_CONV_ROLL64": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and f16x3 and 64x64 and not wgrad or every_route"),
     ({"AZ_ROLL_SEGLEN": "1"}, S1, "stride1_vs_fp64 and not wgrad and not fp32 or residual_handover or dgrad_presplit or full_size"),
+    # multi-plane segments at small shapes (depth 13: 5, 5 and 3 planes; depth 5: one of five): the partials' carried state
+    ({"AZ_ROLL_SEGLEN": "5"}, S1, "forward_batchnorm_partials or forward_affine_residual_relu_epilogue or every_route"),
 ]
 
 
