@@ -17,15 +17,8 @@
 // list is exhausted; az_conv2d_wgrad's unpack kernel transposes [tap][co][ci] -> [co][ci][tap].
 #include <stdlib.h>
 
-#include "az_roll_common.h"
+#include "az_wgrad_common.h"
 #include "az_options.h"
-#include "az_launch_math.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 
 #define W2_WCH 16  // output positions per chunk = one K16 block
 
@@ -54,17 +47,8 @@ conv2d_wgrad_kernel(const W2Args a) {
     // power of two from an amax array (null = scale 1)
     constexpr int NP = (AR == 2 || AR == 3) ? 1 : AR ? 2 : 3;
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR == 1) {
-        const int kc = az_f16_scale_exp(az_amax_read(a.coarse_amax)), kf = az_f16_scale_exp(az_amax_read(a.fine_amax));
-        c_scale = az_pow2(kc); f_scale = az_pow2(kf);
-        o_scale = ldexpf(1.f, -(kc + kf));
-    }
-    if (AR == 3) {
-        const int kc = a.coarse_amax ? az_f16_scale_exp(az_amax_read(a.coarse_amax)) : 0;
-        const int kf = a.fine_amax ? az_f16_scale_exp(az_amax_read(a.fine_amax)) : 0;
-        c_scale = az_pow2(kc); f_scale = az_pow2(kf);
-        o_scale = ldexpf(1.f, -(kc + kf));
-    }
+    if (AR == 1) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
+    if (AR == 3) az_wgrad_scales<true>(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
     constexpr int CY = (KH - 1) / 2, CX = (KW - 1) / 2;
     constexpr int WCH = W2_WCH;
     constexpr int FW = WCH + (KW - 1) * DIL;       // fine positions per staged row
@@ -89,13 +73,13 @@ conv2d_wgrad_kernel(const W2Args a) {
     const int cog = combo / ncn, cig = combo - cog * ncn;
     const int co0 = cog * MT * 32, ci0 = cig * NT * 32;
 
-    f32x16 acc[T];
+    az_f32x16 acc[T];
 #pragma unroll
     for (int t = 0; t < T; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
 
-    // transpose-read geometry (az_conv3d_wgrad.hip): 16-lane group g reads columns 16*(g&1).. of rows
+    // transpose-read geometry (az_wgrad_common.h): 16-lane group g reads columns 16*(g&1).. of rows
     // 8*(g>>1) + {0..3} / {4..7}; lane t = 4q+p of the group supplies row q, columns 4p..4p+3
     const int tq = (lane & 15) >> 2, tp = lane & 3;
     const int tr_col = 16 * ((lane >> 4) & 1) + 4 * tp;
@@ -103,31 +87,11 @@ conv2d_wgrad_kernel(const W2Args a) {
 
     auto split_store = [&](unsigned short *dst_part0, int part_stride, const float4 &v, float scale_) {
         uint2 hi, mid, lo;
-        if (AR == 2) {
-            *reinterpret_cast<uint2 *>(dst_part0) = make_uint2(az_pk_bf16(v.x, v.y), az_pk_bf16(v.z, v.w));
-            return;
-        }
-        if (AR == 3) {
-            *reinterpret_cast<uint2 *>(dst_part0) = make_uint2(az_pk_f16(v.x * scale_, v.y * scale_), az_pk_f16(v.z * scale_, v.w * scale_));
-            return;
-        }
-        if (AR) {
-            az_split2_f16x4(make_float4(v.x * scale_, v.y * scale_, v.z * scale_, v.w * scale_), hi, mid);
-            lo = mid;
-        } else {
-            az_split3_bf16x4(v, hi, mid, lo);
-        }
-        *reinterpret_cast<uint2 *>(dst_part0) = hi;
-        *reinterpret_cast<uint2 *>(dst_part0 + part_stride) = mid;
-        if (!AR) *reinterpret_cast<uint2 *>(dst_part0 + 2 * part_stride) = lo;
+        az_wgrad_split<AR>(v, scale_, hi, mid, lo);
+        az_wgrad_store_parts<AR>(dst_part0, part_stride, hi, mid, lo);
     };
-    auto frag = [&](const unsigned short *img, int r0, int r1) -> bf16x8 {
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + r0 * 32 + tr_col));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + r1 * 32 + tr_col));
-        s16x8 v;
-        v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
-        v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
-        return __builtin_bit_cast(bf16x8, v);
+    auto frag = [&](const unsigned short *img, int r0, int r1) -> az_bf16x8 {
+        return __builtin_bit_cast(az_bf16x8, az_tr16_frag(img + r0 * 32 + tr_col, img + r1 * 32 + tr_col));
     };
     auto slot_of = [&](int fh) -> int { return (fh + 4 * R) % R; };  // fh >= -R always here
 
@@ -199,7 +163,7 @@ conv2d_wgrad_kernel(const W2Args a) {
             commit(y);
             __syncthreads();
             if (y + 1 < h_end) issue(y + 1);  // in flight under this row's MFMAs
-            bf16x8 af[3];
+            az_bf16x8 af[3];
 #pragma unroll
             for (int p = 0; p < NP; ++p) af[p] = frag(sa + mt * ATILE + p * WCH * 32, tr_row, tr_row + 4);
 #pragma unroll
@@ -208,38 +172,17 @@ conv2d_wgrad_kernel(const W2Args a) {
                     sf + (slot_of(y + DIL * (kh - CY) + a.fine_dy) * NT + nt) * FTILE;
 #pragma unroll
                 for (int kw = 0; kw < KW; ++kw) {
-                    bf16x8 bfr[3];
+                    az_bf16x8 bfr[3];
 #pragma unroll
                     for (int p = 0; p < NP; ++p)
                         bfr[p] = frag(frow + p * FW * 32, tr_row + kw * DIL, tr_row + 4 + kw * DIL);
-                    f32x16 c = acc[kh * KW + kw];
-                    if constexpr (AR == 2) {
-                        acc[kh * KW + kw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bfr[0], c, 0, 0, 0);
-                        continue;
-                    }
-                    if constexpr (AR == 3) {
-                        acc[kh * KW + kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bfr[0]), c, 0, 0, 0);
-                        continue;
-                    }
-                    if constexpr (AR == 1) {
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(az_f16x8, af[1]), __builtin_bit_cast(az_f16x8, bfr[0]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bfr[1]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bfr[0]), c, 0, 0, 0);
-                        acc[kh * KW + kw] = c;
-                        continue;
-                    }
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bfr[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bfr[2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bfr[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bfr[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bfr[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bfr[0], c, 0, 0, 0);
-                    acc[kh * KW + kw] = c;
+                    az_wgrad_chain<AR>(acc[kh * KW + kw], af, bfr);
                 }
             }
         }
     }
-    // D[i][j]: i = coarse channel (row map of the 32x32 MFMA), j = fine channel (lane & 31)
+    // D[i][j]: i = coarse channel (az_mfma32_c_row), j = fine channel (lane & 31); written out: as a shared function the flush
+    // moves the registers of 22 of the 40 instantiations by one or two
 #pragma unroll
     for (int t = 0; t < T; ++t) {
 #pragma unroll
@@ -301,9 +244,6 @@ static int dispatch_tiles(const W2Args &a, hipStream_t s) {
     if (n2) return launch_w2<1, 2, KH, KW, DIL>(a, s);
     return launch_w2<1, 1, KH, KW, DIL>(a, s);
 }
-
-int az_conv2d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine, int B, int H, int W, int cm, int cn,
-                               int cs_c, int cs_f, hipStream_t s, const float *coarse_amax, const float *fine_amax);
 
 // the 3x3 d1 layers with 32 / 64 channels on either side go to az_conv2d_wgrad16.hip (AZ_CONV2D_WGRAD_R16=0: off)
 static bool wgrad2d_on_r16(int cm, int cn, int kh, int kw, int dilation) {

@@ -6,7 +6,7 @@
 //
 //   * a workgroup = 4 waves owns ONE 32 x 32 (co, ci) tile -- wave (mi, ni) its 16 x 16 block for all 9 taps
 //     (36 accumulator registers) -- and shares every staged byte; 64-channel layers are 2 x 2 such tiles in the grid;
-//   * K = 32 positions per v_mfma_f32_16x16x32_bf16 = two adjacent dy rows x 16 positions; a step is 9 taps x 6 MFMAs
+//   * K = 32 positions per 16x16x32 bf16 MFMA = two adjacent dy rows x 16 positions; a step is 9 taps x 6 MFMAs
 //     per wave and needs the dy pair (double-buffered) and the 4-row window of x rows (a ring of six), of which only
 //     the pair and two x rows are new: 68 positions staged per 54 MFMAs x 4 waves (az_conv2d_wgrad.hip: 34 per 54
 //     MFMAs of ONE wave for the 32 -> 32 layers, between two barriers);
@@ -14,22 +14,15 @@
 //     validity (zero padding in y / x) through buffer instructions with out-of-range offsets: a step is one basic block;
 //   * workgroups walk (image, 16-position chunk, row segment) columns and flush their 9 x 32 x 32 block once, with
 //     float atomics, into the tap-major workspace of az_conv2d_wgrad.hip ([tap][CM][CN]).
-// Arithmetic per K block: the six-MFMA chain of the other weight-gradient kernels (smallest terms first, fp32
+// Arithmetic per K block: the six-MFMA chain of az_wgrad_common.h (smallest terms first, fp32
 // accumulate).  LDS 33 KB, so three to four workgroups share a CU (the 3-D kernel: 77 KB, two).
 #include <stdlib.h>
 
-#include "az_roll_common.h"
-#include "az_launch_math.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
+#include "az_wgrad_common.h"
 
 #define V16_POS 16                       // positions of a dy row per step
 #define V16_FW (V16_POS + 2)             // x positions per staged row
-#define V16_ROWB 64                      // bytes of one (position, 32 channels) bf16 row
+#define V16_ROWB AZ_W16_ROWB             // bytes of one (position, 32 channels) bf16 row
 #define V16_CBUF (3 * 32 * V16_ROWB)     // one dy buffer: [part][k = 2 rows x 16][32 ch]      6 144 B
 #define V16_FROW (3 * V16_FW * V16_ROWB) // one x row: [part][18 positions][32 ch]              3 456 B
 #define V16_RING 6
@@ -54,11 +47,7 @@ __global__ void __launch_bounds__(256, 3)
 conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
     constexpr int NP = AR ? 2 : 3;
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR) {
-        const int kc = az_f16_scale_exp(az_amax_read(a.coarse_amax)), kf = az_f16_scale_exp(az_amax_read(a.fine_amax));
-        c_scale = az_pow2(kc); f_scale = az_pow2(kf);
-        o_scale = ldexpf(1.f, -(kc + kf));
-    }
+    if (AR) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
     __shared__ __attribute__((aligned(16))) unsigned char lds[V16_LDS + 64];  // + a sink for the lanes of a partial piece
     unsigned char *const cbuf = lds;                  // [2][V16_CBUF]
     unsigned char *const fring = lds + 2 * V16_CBUF;  // [slot][V16_FROW]
@@ -74,26 +63,11 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // transposing-read geometry and the row-half swap against the 2-way conflicts: az_conv3d_wgrad16.hip
-    const int oct = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
-    const unsigned a_lane = (unsigned)(8 * oct + tq) * V16_ROWB + (((unsigned)(16 * mi + 4 * tp) * 2) ^ ((unsigned)(oct & 1) << 5));
-    const int rp = oct >> 1;
-    unsigned b_off[3][2];
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const unsigned rowi = (unsigned)(8 * (oct & 1) + tq + kw + 4 * h2);
-            b_off[kw][h2] = rowi * V16_ROWB + (((unsigned)(16 * ni + 4 * tp) * 2) ^ (((rowi >> 3) & 1u) << 5));
-        }
-    auto frag2 = [&](const unsigned char *lo, const unsigned char *hi) -> az_bf16x8 {
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(lo));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(hi));
-        s16x8 v;
-        v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
-        v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
-        return __builtin_bit_cast(az_bf16x8, v);
-    };
+    // transposing-read geometry and the row-half swap against the 2-way conflicts: az_launch_math.h
+    const AzW16Lanes g = az_w16_lanes(lane, 16 * mi, 16 * ni);
+    const unsigned a_lane = g.a_lane;
+    const int rp = g.rp;
+    const auto &b_off = g.b_off;
 
     const unsigned img_c = (unsigned)a.H * a.W * a.cs_c * 4u, img_f = (unsigned)a.H * a.W * a.cs_f * 4u;
     for (long long col = wg; col < a.ncols; col += a.wgs) {
@@ -132,16 +106,8 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
         auto commit_piece = [&](int it, int cbuf_idx, int frow0) {
             const int q = tid + 256 * it;
             uint2 hi, mid, lo;
-            if (AR) {
-                float4 v = __builtin_bit_cast(float4, pre[it]);
-                const float sc_ = it == 0 ? c_scale : f_scale;
-                v.x *= sc_; v.y *= sc_; v.z *= sc_; v.w *= sc_;
-                az_split2_f16x4(v, hi, mid);
-                lo = mid;
-            } else {
-                az_split3_bf16x4(__builtin_bit_cast(float4, pre[it]), hi, mid, lo);
-            }
-            unsigned char *dst;
+            az_wgrad_split<AR>(pre[it], it == 0 ? c_scale : f_scale, hi, mid, lo);
+            unsigned char *dst;  // az_w16_piece_off written out (called as a function it moves the registers: <1> 117 -> 116, <0> 133 -> 132)
             unsigned part_stride;
             if (it == 0) {
                 dst = cbuf + cbuf_idx * V16_CBUF + (q >> 3) * V16_ROWB + (((q & 7) * 8) ^ ((((q >> 3) >> 3) & 1) << 5));
@@ -154,9 +120,7 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
                 part_stride = V16_FW * V16_ROWB;
             }
             if (q >= V16_NQ) { dst = lds + V16_LDS + (tid & 7) * 8; part_stride = 0; }  // (no branch: a step stays one block)
-            *reinterpret_cast<uint2 *>(dst) = hi;
-            *reinterpret_cast<uint2 *>(dst + part_stride) = mid;
-            if (!AR) *reinterpret_cast<uint2 *>(dst + 2 * part_stride) = lo;
+            az_wgrad_store_parts<AR>(dst, part_stride, hi, mid, lo);
         };
 
         // ---- prologue: the window of the first step (x rows h0-1 .. h0+2, dy rows h0, h0+1), then the request for the next ----
@@ -183,14 +147,14 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
 
             az_bf16x8 af[3];
 #pragma unroll
-            for (int p = 0; p < NP; ++p) af[p] = frag2(ca + p * 32 * V16_ROWB, ca + p * 32 * V16_ROWB + 4 * V16_ROWB);
+            for (int p = 0; p < NP; ++p) af[p] = __builtin_bit_cast(az_bf16x8, az_tr16_frag(ca + p * 32 * V16_ROWB, ca + p * 32 * V16_ROWB + 4 * V16_ROWB));
             az_bf16x8 bf[2][3];
             auto load_b = [&](az_bf16x8 (&bq)[3], int t) {
                 const int kh = t / 3, kw = t % 3;
                 const unsigned char *fp = fring + fb[kh];
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    bq[p] = frag2(fp + b_off[kw][0] + p * V16_FW * V16_ROWB, fp + b_off[kw][1] + p * V16_FW * V16_ROWB);
+                    bq[p] = __builtin_bit_cast(az_bf16x8, az_tr16_frag(fp + b_off[kw][0] + p * V16_FW * V16_ROWB, fp + b_off[kw][1] + p * V16_FW * V16_ROWB));
             };
             load_b(bf[0], 0);
 #pragma unroll
@@ -198,21 +162,7 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (t + 1 < 9) load_b(bf[(t + 1) & 1], t + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                f32x4 c = acc[t];
-                const az_bf16x8(&bq)[3] = bf[t & 1];
-                if constexpr (AR) {
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[1]), __builtin_bit_cast(az_f16x8, bq[0]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bq[1]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bq[0]), c, 0, 0, 0);
-                } else {
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bq[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[0], c, 0, 0, 0);
-                }
-                acc[t] = c;
+                az_wgrad_chain<AR>(acc[t], af, bf[t & 1]);
                 // the set of the next step (requested a step ago): one piece after each of the taps 0, 2, 4; then the
                 // request for the step after that
                 if (t <= 4 && !(t & 1)) {
@@ -229,12 +179,7 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
     }
     // D[i][j]: i = output channel co0 + 16 mi + 4 (lane >> 4) + r, j = input channel ci0 + 16 ni + (lane & 15)
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = co0 + 16 * mi + 4 * (lane >> 4) + r;
-            atomicAdd(&a.ws[((size_t)t * a.CM + m) * a.CN + ci0 + 16 * ni + (lane & 15)], AR ? acc[t][r] * o_scale : acc[t][r]);
-        }
+    for (int t = 0; t < 9; ++t) az_wgrad_flush16<AR != 0>(a.ws, t, co0 + 16 * mi, ci0 + 16 * ni, a.CM, a.CN, acc[t], o_scale, lane);
 }
 
 // ---- round 5: the 64 -> 64 layers (layer2: 32 of the 39 launches per step) as ONE 64 x 64 tile per workgroup -------------------
@@ -265,8 +210,8 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
 
 __global__ void __launch_bounds__(512, 1)
 conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
-    const int kc = az_f16_scale_exp(az_amax_read(a.coarse_amax)), kf = az_f16_scale_exp(az_amax_read(a.fine_amax));
-    const float c_scale = az_pow2(kc), f_scale = az_pow2(kf), o_scale = ldexpf(1.f, -(kc + kf));
+    float c_scale, f_scale, o_scale;
+    az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
     __shared__ __attribute__((aligned(16))) unsigned char lds[X16_LDS + 64];  // + a sink for the lanes of the partial piece
     unsigned char *const cbuf = lds;                  // [2][X16_CBUF]
     unsigned char *const fring = lds + 2 * X16_CBUF;  // [slot][X16_FROW]
@@ -281,13 +226,12 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
         for (int mb = 0; mb < 4; ++mb) acc[i][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // transposing-read geometry of the kernel above inside one 32-channel image
-    const int oct = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
-    const int rp = oct >> 1;
+    const int oct = lane >> 4, rp = oct >> 1;
     // dy blocks mb = 2 half + h16: image `half`, channels 16 h16 ..: the two h16 bases differ in bit 5 of the in-row offset
     unsigned a_lane[2];
 #pragma unroll
     for (int h16 = 0; h16 < 2; ++h16)
-        a_lane[h16] = (unsigned)(8 * oct + tq) * V16_ROWB + (((unsigned)(16 * h16 + 4 * tp) * 2) ^ ((unsigned)(oct & 1) << 5));
+        a_lane[h16] = az_w16_read_off(lane, 8 * oct, 16 * h16);
     // x block nb, tap i of this wave (tap = t0 + 2 i, clamped to 8): per-lane byte offset inside a ring slot for the two row
     // groups of a fragment, and kh in two bits of a scalar -- a step stays straight-line code although wv is a run-time value
     unsigned boff[5][2], khpack = 0;
@@ -296,20 +240,9 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
         const int t = min(t0 + 2 * i, 8);
         const int kh = t / 3, kw = t % 3;
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const unsigned rowi = (unsigned)(8 * (oct & 1) + tq + kw + 4 * h2);
-            boff[i][h2] = (unsigned)(nb >> 1) * X16_FIMG + rowi * V16_ROWB + (((unsigned)(16 * (nb & 1) + 4 * tp) * 2) ^ (((rowi >> 3) & 1u) << 5));
-        }
+        for (int h2 = 0; h2 < 2; ++h2) boff[i][h2] = (unsigned)(nb >> 1) * X16_FIMG + az_w16_read_off(lane, 8 * (oct & 1) + kw + 4 * h2, 16 * (nb & 1));
         khpack |= (unsigned)kh << (2 * i);
     }
-    auto frag2 = [&](const unsigned char *lo, const unsigned char *hi) -> az_f16x8 {
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(lo));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(hi));
-        s16x8 v;
-        v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
-        v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
-        return __builtin_bit_cast(az_f16x8, v);
-    };
 
     const unsigned img_c = (unsigned)a.H * a.W * a.cs_c * 4u, img_f = (unsigned)a.H * a.W * a.cs_f * 4u;
     for (long long col = blockIdx.x; col < a.ncols; col += a.wgs) {
@@ -348,9 +281,9 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
         auto commit_piece = [&](int it, int cbuf_idx, int frow0) {
             const int q = tid + 512 * it;
             uint2 hi, lo;
-            az_stage_f16x4<false>(pre[it], it == 0 ? c_scale : f_scale, hi, lo);
+            az_wgrad_split<1>(pre[it], it == 0 ? c_scale : f_scale, hi, lo, lo);
             const int f4 = q & 15, half = f4 >> 3, j8 = f4 & 7;  // 32-channel image, 8-byte piece inside its row
-            unsigned char *dst;
+            unsigned char *dst;  // az_w16_piece_off written out (called as a function: 196 -> 199 registers)
             unsigned part_stride;
             if (it == 0) {
                 const int k = q >> 4;
@@ -364,8 +297,7 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
                 part_stride = V16_FW * V16_ROWB;
             }
             if (q >= X16_NQ) { dst = lds + X16_LDS + (tid & 7) * 8; part_stride = 0; }  // (no branch: a step stays one block)
-            *reinterpret_cast<uint2 *>(dst) = hi;
-            *reinterpret_cast<uint2 *>(dst + part_stride) = lo;
+            az_wgrad_store_parts<1>(dst, part_stride, hi, lo, lo);
         };
 
         // ---- prologue: the window of the first step (x rows h0-1 .. h0+2, dy rows h0, h0+1), then the request for the next ----
@@ -391,7 +323,7 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     const unsigned char *cp = cb + (mb >> 1) * X16_CIMG + p * 32 * V16_ROWB + a_lane[mb & 1];
-                    af[mb][p] = frag2(cp, cp + 4 * V16_ROWB);
+                    af[mb][p] = __builtin_bit_cast(az_f16x8, az_tr16_frag(cp, cp + 4 * V16_ROWB));
                 }
             az_f16x8 bf[2][2];
             auto load_b = [&](az_f16x8 (&bq)[2], int i) {
@@ -400,7 +332,8 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
                 r = r >= V16_RING ? r - V16_RING : r;
                 const unsigned char *fp = fring + (unsigned)r * X16_FROW;
 #pragma unroll
-                for (int p = 0; p < 2; ++p) bq[p] = frag2(fp + boff[i][0] + p * V16_FW * V16_ROWB, fp + boff[i][1] + p * V16_FW * V16_ROWB);
+                for (int p = 0; p < 2; ++p)
+                    bq[p] = __builtin_bit_cast(az_f16x8, az_tr16_frag(fp + boff[i][0] + p * V16_FW * V16_ROWB, fp + boff[i][1] + p * V16_FW * V16_ROWB));
             };
             load_b(bf[0], 0);
 #pragma unroll
@@ -410,13 +343,7 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
                 const az_f16x8(&bq)[2] = bf[i & 1];
 #pragma unroll
-                for (int mb = 0; mb < 4; ++mb) {
-                    f32x4 c = acc[i][mb];  // lo*hi, hi*lo, hi*hi chained into the running accumulator (smallest first)
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][1], bq[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][0], bq[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][0], bq[0], c, 0, 0, 0);
-                    acc[i][mb] = c;
-                }
+                for (int mb = 0; mb < 4; ++mb) az_wgrad_chain<1>(acc[i][mb], af[mb], bq);  // one chain per M block
                 // the set of the next step (requested a step ago): one piece after each of the pairs 0, 1, 2; then the request
                 // for the step after that
                 if (i <= 2) {
@@ -437,12 +364,7 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
         const int t = t0 + 2 * i;
         if (t > 8) break;  // (wave-uniform)
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = 16 * mb + 4 * (lane >> 4) + r;
-                atomicAdd(&a.ws[((size_t)t * 64 + m) * 64 + 16 * nb + (lane & 15)], acc[i][mb][r] * o_scale);
-            }
+        for (int mb = 0; mb < 4; ++mb) az_wgrad_flush16<true>(a.ws, t, 16 * mb, 16 * nb, 64, 64, acc[i][mb], o_scale, lane);
     }
 }
 
@@ -450,7 +372,7 @@ conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
 int az_conv2d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine, int B, int H, int W, int cm, int cn,
                                int cs_c, int cs_f, hipStream_t s, const float *coarse_amax, const float *fine_amax) {
     if (!((cm == 32 || cm == 64) && (cn == 32 || cn == 64))) return AZ_EUNSUPPORTED;
-    if ((long long)H * W * (cs_c > cs_f ? cs_c : cs_f) * 4 >= 0xffffff00LL) return AZ_EUNSUPPORTED;
+    if (!az_fits_buffer_offset((long long)H * W * (cs_c > cs_f ? cs_c : cs_f) * 4)) return AZ_EUNSUPPORTED;
     Wg2dArgs a{};
     a.coarse = coarse; a.fine = fine; a.ws = ws; a.coarse_amax = coarse_amax; a.fine_amax = fine_amax;
     a.B = B; a.H = H; a.W = W; a.CM = cm; a.CN = cn; a.cs_c = cs_c; a.cs_f = cs_f;

@@ -20,11 +20,8 @@
 // the flops.  az_conv3d_wgrad_unpack transposes [k][m][n] -> [m][n][k].
 #include <stdlib.h>
 
-#include "az_roll_common.h"
+#include "az_wgrad_common.h"
 #include "az_options.h"
-#include "az_launch_math.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // coarse positions per staged chunk (even).  PSMNet's widths are 240 / 120 / 60: 30 and 20
 // divides them exactly (no MFMA on padding positions); the stride-2 kernels keep 16 (a wider
@@ -81,8 +78,9 @@ conv3d_wgrad_kernel(const WgArgs a) {
     __shared__ __attribute__((aligned(16))) float sf[3 * FW * 32];  // row fh lives in slot fh mod 3
 
     const int lane = threadIdx.x, row = lane & 31, half = lane >> 5;
-    // blocks b and b+8 share an XCD: the NCOMBO waves that walk the SAME work list (same
-    // coarse rows, neighbouring fine planes) are given ids 8 apart so they share one L2.
+    // blocks b and b+8 share an XCD: the NCOMBO waves that walk the SAME work list (same coarse rows, neighbouring fine planes)
+    // are given ids 8 apart so they share one L2.  (This decode, `issue` and the flush stay written out in each one-kd kernel:
+    // as shared functions they move the registers of the stride-2 instantiations, 153 -> 155 / 167, 149 -> 155, 256 -> 4 spilled.)
     const int grp = blockIdx.x / (8 * NCOMBO), rem = blockIdx.x % (8 * NCOMBO);
     int combo = rem >> 3;
     const int widx = grp * 8 + (rem & 7);
@@ -90,7 +88,7 @@ conv3d_wgrad_kernel(const WgArgs a) {
     const int mt = combo % MT;
     const int kd = combo / MT;
 
-    f32x16 acc[9];
+    az_f32x16 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -199,17 +197,13 @@ conv3d_wgrad_kernel(const WgArgs a) {
 
 
 // ---- bf16x6 variant ------------------------------------------------------------------------
-// Same decomposition, but the products run on v_mfma_f32_32x32x16_bf16 with both operands split
+// Same decomposition, but the products run on the 32x32x16 bf16 MFMA with both operands split
 // exactly into three bf16 parts (hi, mid, lo; six significant partial products, fp32
 // accumulation -- see az_conv3d.hip).  K = 16 POSITIONS per MFMA, so a lane needs 8 consecutive
 // positions of its channel: the staged [position][channel] bf16 tiles are read with
 // ds_read_b64_tr_b16 (the hardware transpose read: per 16-lane group, lane 4q+p gives the
 // address of row q / columns 4p..4p+3 and lane i receives column i of the 4 rows).  Rows are
 // addressed individually, which also covers the stride-2 position map and the kw tap shift.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 
 #define X6_WCH 16  // coarse positions per chunk = one K16 block
 
@@ -221,12 +215,7 @@ conv3d_wgrad_x6_kernel(const WgArgs a) {
     constexpr int WCH = X6_WCH;
     constexpr int NP = AR ? 2 : 3;
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR) {
-        const int kc = az_f16_scale_exp(az_amax_read(a.coarse_amax));
-        const int kf = az_f16_scale_exp(az_amax_read(a.fine_amax));
-        c_scale = az_pow2(kc); f_scale = az_pow2(kf);
-        o_scale = ldexpf(1.f, -(kc + kf));
-    }
+    if (AR) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
     constexpr int FW = S * (WCH - 1) + 3;  // fine positions per staged row
     constexpr int MT = CM / 32, NT = CN / 32, NCOMBO = 3 * MT * NT;
     constexpr int NEW = S;
@@ -244,7 +233,7 @@ conv3d_wgrad_x6_kernel(const WgArgs a) {
     const int mt = combo % MT;
     const int kd = combo / MT;
 
-    f32x16 acc[9];
+    az_f32x16 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -258,26 +247,13 @@ conv3d_wgrad_x6_kernel(const WgArgs a) {
     const int tr_row = 8 * (lane >> 5) + tq;  // + 4 for the second read
 
     auto split_store = [&](unsigned short *dst_part0, int part_stride, const float4 &v, float scale_) {
-        // exact 3-way bf16 split (or the scaled two-part fp16 split); dst_part0 points at 4 channels of part 0
-        uint2 hi, mid, lo;
-        if (AR) {
-            az_split2_f16x4(make_float4(v.x * scale_, v.y * scale_, v.z * scale_, v.w * scale_), hi, mid);
-            lo = mid;
-        } else {
-            az_split3_bf16x4(v, hi, mid, lo);
-        }
-        *reinterpret_cast<uint2 *>(dst_part0) = hi;
-        *reinterpret_cast<uint2 *>(dst_part0 + part_stride) = mid;
-        if (!AR) *reinterpret_cast<uint2 *>(dst_part0 + 2 * part_stride) = lo;
+        uint2 hi, mid, lo;  // dst_part0 points at 4 channels of part 0
+        az_wgrad_split<AR>(v, scale_, hi, mid, lo);
+        az_wgrad_store_parts<AR>(dst_part0, part_stride, hi, mid, lo);
     };
-    // fragment of 8 consecutive K rows (positions) for this lane's column, rows given by rowfn(k)
-    auto frag = [&](const unsigned short *img, int r0, int r1) -> bf16x8 {
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + r0 * 32 + tr_col));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + r1 * 32 + tr_col));
-        s16x8 v;
-        v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
-        v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
-        return __builtin_bit_cast(bf16x8, v);
+    // fragment of 8 consecutive K rows (positions) for this lane's column: rows r0 .. r0 + 3 and r1 .. r1 + 3
+    auto frag = [&](const unsigned short *img, int r0, int r1) -> az_bf16x8 {
+        return __builtin_bit_cast(az_bf16x8, az_tr16_frag(img + r0 * 32 + tr_col, img + r1 * 32 + tr_col));
     };
 
     for (long long item = widx; item < a.nitems; item += a.waves_per_combo) {
@@ -355,7 +331,7 @@ conv3d_wgrad_x6_kernel(const WgArgs a) {
             if (ch + 1 < h_end) issue(ch + 1);
             const int s0 = (S * ch - 1 + 3) % 3;  // slot of kh = 0
             // A fragments (coarse): parts hi/mid/lo, K rows = positions 8*(lane>>5) + 0..7
-            bf16x8 af[3];
+            az_bf16x8 af[3];
 #pragma unroll
             for (int p = 0; p < NP; ++p) af[p] = frag(sa + p * WCH * 32, tr_row, tr_row + 4);
 #pragma unroll
@@ -363,26 +339,11 @@ conv3d_wgrad_x6_kernel(const WgArgs a) {
                 const unsigned short *frow = sf + ((s0 + kh) % 3) * 3 * FW * 32;
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw) {
-                    bf16x8 bfr[3];
+                    az_bf16x8 bfr[3];
 #pragma unroll
                     for (int p = 0; p < NP; ++p)
                         bfr[p] = frag(frow + p * FW * 32, S * tr_row + kw, S * (tr_row + 4) + kw);
-                    f32x16 c = acc[kh * 3 + kw];
-                    if constexpr (AR) {
-                        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, af[1]), __builtin_bit_cast(h8, bfr[0]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, af[0]), __builtin_bit_cast(h8, bfr[1]), c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, af[0]), __builtin_bit_cast(h8, bfr[0]), c, 0, 0, 0);
-                        acc[kh * 3 + kw] = c;
-                        continue;
-                    }
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2], bfr[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bfr[2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bfr[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1], bfr[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bfr[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0], bfr[0], c, 0, 0, 0);
-                    acc[kh * 3 + kw] = c;
+                    az_wgrad_chain<AR>(acc[kh * 3 + kw], af, bfr);
                 }
             }
         }
@@ -422,7 +383,7 @@ conv3d_wgrad_x6_fw_kernel(const WgArgs a) {
     const int mt = combo % MT;
     const int kd = combo / MT;
 
-    f32x16 acc[9];
+    az_f32x16 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -433,18 +394,11 @@ conv3d_wgrad_x6_fw_kernel(const WgArgs a) {
     const int tr_row = 8 * (lane >> 5) + tq;
     auto split_store = [&](unsigned short *dst_part0, int part_stride, const float4 &v) {
         uint2 hi, mid, lo;
-        az_split3_bf16x4(v, hi, mid, lo);
-        *reinterpret_cast<uint2 *>(dst_part0) = hi;
-        *reinterpret_cast<uint2 *>(dst_part0 + part_stride) = mid;
-        *reinterpret_cast<uint2 *>(dst_part0 + 2 * part_stride) = lo;
+        az_wgrad_split<0>(v, 1.f, hi, mid, lo);
+        az_wgrad_store_parts<0>(dst_part0, part_stride, hi, mid, lo);
     };
-    auto frag = [&](const unsigned short *img, int r0, int r1) -> bf16x8 {
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + r0 * 32 + tr_col));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + r1 * 32 + tr_col));
-        s16x8 v;
-        v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
-        v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
-        return __builtin_bit_cast(bf16x8, v);
+    auto frag = [&](const unsigned short *img, int r0, int r1) -> az_bf16x8 {
+        return __builtin_bit_cast(az_bf16x8, az_tr16_frag(img + r0 * 32 + tr_col, img + r1 * 32 + tr_col));
     };
 
     for (long long item = widx; item < a.nitems; item += a.waves_per_combo) {
@@ -511,7 +465,7 @@ conv3d_wgrad_x6_fw_kernel(const WgArgs a) {
             if (r + 1 <= h_end) issue(r + 1);
             if (r < 0 || r >= a.Hf) continue;  // a zero fine row adds nothing (wave-uniform)
             // coarse fragments of rows r+1 (kh 0), r (kh 1), r-1 (kh 2): parts hi/mid/lo
-            bf16x8 af[3][3];
+            az_bf16x8 af[3][3];
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh) {
                 const unsigned short *arow = sa + ((r + 1 - kh + 3) % 3) * 3 * WCH * 32;
@@ -521,20 +475,13 @@ conv3d_wgrad_x6_fw_kernel(const WgArgs a) {
             const bool ok0 = r + 1 >= h_beg && r + 1 < h_end, ok1 = r >= h_beg && r < h_end, ok2 = r - 1 >= h_beg && r - 1 < h_end;
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                bf16x8 bfr[3];
+                az_bf16x8 bfr[3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p) bfr[p] = frag(sf + p * FW * 32, tr_row + kw, tr_row + 4 + kw);
 #pragma unroll
                 for (int kh = 0; kh < 3; ++kh) {
                     if (!(kh == 0 ? ok0 : kh == 1 ? ok1 : ok2)) continue;  // coarse row outside the segment (wave-uniform)
-                    f32x16 c = acc[kh * 3 + kw];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kh][2], bfr[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kh][0], bfr[2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kh][1], bfr[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kh][1], bfr[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kh][0], bfr[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kh][0], bfr[0], c, 0, 0, 0);
-                    acc[kh * 3 + kw] = c;
+                    az_wgrad_chain<0>(acc[kh * 3 + kw], af[kh], bfr);
                 }
             }
         }
@@ -604,13 +551,11 @@ static int launch_wgrad(WgArgs a, hipStream_t s) {
     return az_launch_status();
 }
 
-// all 27 taps per wave on 16x16x32 tiles, four waves sharing one staged set (az_conv3d_wgrad16.hip)
-int az_conv3d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine, int B, int cm, int cn, int D, int H, int W, hipStream_t s,
-                               const float *coarse_amax = nullptr, const float *fine_amax = nullptr, int split_mask = 0);
-
-// stride 2, f16x3: eight waves sharing one staged set (az_conv3d_wgrad16s2.hip)
-int az_conv3d_wgrad_s2r16_launch(float *ws, const float *coarse, const float *fine, int B, int cm, int cn, int Dc, int Hc, int Wc,
-                                 int Df, int Hf, int Wf, hipStream_t s, const float *coarse_amax, const float *fine_amax, int split_mask);
+int az_wgrad_unpack_launch(float *grad_w, const float *ws, int cm, int cn, hipStream_t s) {
+    const int total = cm * cn * 27;
+    hipLaunchKernelGGL(wgrad_unpack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, grad_w, ws, cm, cn);
+    return az_launch_status();
+}
 
 extern "C" long long az_conv3d_wgrad_workspace(int cm, int cn) {
     if (cm <= 0 || cn <= 0 || cm % 32 || cn % 32) return AZ_EINVAL;
@@ -640,11 +585,7 @@ extern "C" int az_conv3d_wgrad(float *grad_w, float *workspace, long long worksp
         if (r16 && precision == 1 && stride == 1 && (cm == 32 || cm == 64) && (cn == 32 || cn == 64) && (r16 >= 2 || (cm == 32 && cn == 32)) &&
             Dc == Df && Hc == Hf && Wc == Wf) {
             rc = az_conv3d_wgrad_r16_launch(workspace, coarse, fine, B, cm, cn, Dc, Hc, Wc, s);
-            if (rc == AZ_OK) {
-                const int total = cm * cn * 27;
-                hipLaunchKernelGGL(wgrad_unpack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, grad_w, workspace, cm, cn);
-                return az_launch_status();
-            }
+            if (rc == AZ_OK) return az_wgrad_unpack_launch(grad_w, workspace, cm, cn, s);
             // AZ_EUNSUPPORTED: a batch element beyond the kernel's 32-bit buffer offsets (>= 4 GiB) -- the flat-address
             // kernels below take it
             if (rc != AZ_EUNSUPPORTED) return rc;
@@ -658,10 +599,7 @@ extern "C" int az_conv3d_wgrad(float *grad_w, float *workspace, long long worksp
     WG_CASE(32, 32) WG_CASE(32, 64) WG_CASE(64, 32) WG_CASE(64, 64)
 #undef WG_CASE
     if (rc != AZ_OK) return rc;
-    const int total = cm * cn * 27;
-    hipLaunchKernelGGL(wgrad_unpack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, grad_w,
-                       workspace, cm, cn);
-    return az_launch_status();
+    return az_wgrad_unpack_launch(grad_w, workspace, cm, cn, s);
 }
 
 // f16x3 weight gradient (include/azhip.h): the stride-1 layers with 32 / 64 channels on either side
@@ -715,7 +653,5 @@ extern "C" int az_conv3d_wgrad_f16(float *grad_w, float *workspace, long long wo
     }
     if (rc != AZ_OK) return rc;
     if (!grad_w) return az_launch_status();
-    const int total = cm * cn * 27;
-    hipLaunchKernelGGL(wgrad_unpack_kernel, dim3((total + 255) / 256), dim3(256), 0, s, grad_w, workspace, cm, cn);
-    return az_launch_status();
+    return az_wgrad_unpack_launch(grad_w, workspace, cm, cn, s);
 }

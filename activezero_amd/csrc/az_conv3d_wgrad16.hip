@@ -8,7 +8,7 @@
 // az_conv3d_wgrad.hip gives a wave ONE kd (nine 32x32 accumulators = 144 registers): the coarse row is fetched, split
 // into its bf16 triplet and written to LDS by three waves, every fine row by three waves too, and that staging sits
 // between two barriers of a one-wave workgroup (20-30 % of the kernel, profiles/r02_clock_pipe_ablation.md section 7).
-// Here, on v_mfma_f32_16x16x32_bf16:
+// Here, on the 16x16x32 bf16 MFMA:
 //   * a wave owns a 16 x 16 block (half of the coarse channels x half of the fine channels) of ALL 27 taps: 27 x 4 = 108
 //     accumulator registers; four waves = one workgroup cover 32 x 32 and share every staged byte;
 //   * K = 32 positions per MFMA = two adjacent coarse rows x 16 positions (240 = 15 x 16: no padded positions); a step
@@ -19,7 +19,7 @@
 //     therefore vmcnt bookkeeping go through buffer instructions with out-of-range offsets: a step is one basic block;
 //   * workgroups are persistent: each walks a list of (batch, coarse depth, 16-position chunk) columns and flushes its
 //     27 x 32 x 32 block once, with float atomics, into the tap-major workspace of az_conv3d_wgrad.hip.
-// Arithmetic per K block: the six-MFMA chain of az_conv3d_wgrad.hip (smallest terms first, fp32 accumulate).
+// Arithmetic per K block: the six-MFMA chain of az_wgrad_common.h (smallest terms first, fp32 accumulate).
 //
 // Measured (B=4, V0; profiles/r03_roll_kernel_notes.md section 5): 1.65-1.74 ms against 1.76-1.80 ms for the one-kd-per-
 // wave kernel on the same boxes -- staging is now a third per MFMA and hidden, LDS bank conflicts are gone (46 % of the
@@ -29,17 +29,12 @@
 // with recomputed addresses +13 %).
 #include <stdlib.h>
 
-#include "az_roll_common.h"
+#include "az_wgrad_common.h"
 #include "az_options.h"
-#include "az_launch_math.h"
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 
 #define W16_POS 16                       // positions of a coarse row per step
 #define W16_FW (W16_POS + 2)             // fine positions per staged row
-#define W16_ROWB 64                      // bytes of one (position, 32 channels) bf16 row
+#define W16_ROWB AZ_W16_ROWB             // bytes of one (position, 32 channels) bf16 row
 #define W16_CBUF (3 * 32 * W16_ROWB)     // one coarse buffer: [part][k = 2 rows x 16][32 ch]      6 144 B
 #define W16_FROW (3 * W16_FW * W16_ROWB) // one fine row: [part][18 positions][32 ch]              3 456 B
 #define W16_RING 6
@@ -86,23 +81,13 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
 #pragma unroll
     for (int t = 0; t < 27; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR) {  // wave-uniform power-of-two operand scales
-        const int kc = az_f16_scale_exp(az_amax_read(a.coarse_amax));
-        const int kf = az_f16_scale_exp(az_amax_read(a.fine_amax));
-        c_scale = az_pow2(kc); f_scale = az_pow2(kf);
-        o_scale = ldexpf(1.f, -(kc + kf));
-    }
+    if (AR) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
 
-    // transposing-read geometry (ds_read_b64_tr_b16 on a [k][32 ch] bf16 image): a 16-lane group (= one K octet) reads
-    // 4 k-rows x 16 channels; lane 4q + p supplies the address of row q, channels 4p..4p+3 and receives channel (lane & 15)
-    // Banks: a 64-B row is 16 banks, so rows r and r + 8 of an image fall on the same banks, and the two octets of a
-    // 32-lane half read exactly such rows (k-rows 8 apart): a 2-way conflict on every read (measured: 46 % of the LDS
-    // cycles).  The two 32-byte channel halves of a row are therefore swapped on rows with bit 3 set (writes and reads
-    // XOR the in-row byte offset with ((row >> 3) & 1) << 5).
+    // transposing-read geometry and the row-half swap against bank conflicts: az_w16_lanes (az_launch_math.h), written out
+    // (called as a function it moves this kernel's registers: <1, .> 244 -> 243, <0, 0> 11 -> 7 spilled)
     const int oct = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
     const unsigned a_lane = (unsigned)(8 * oct + tq) * W16_ROWB + (((unsigned)(16 * mi + 4 * tp) * 2) ^ ((unsigned)(oct & 1) << 5));
-    // fine: octet -> (row of the pair, position 8 (oct & 1) ..): the row-in-window part is added per step (ring slots);
-    // the LDS row of a read is position + kw (+ 4 for the second half of a fragment): offsets per kw, built once
+    // fine: the offsets inside one staged row, per kw; the row-in-window part is added per step (ring slots)
     const int rp = oct >> 1;
     unsigned b_off[3][2];
 #pragma unroll
@@ -112,15 +97,6 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
             const unsigned rowi = (unsigned)(8 * (oct & 1) + tq + kw + 4 * h2);
             b_off[kw][h2] = rowi * W16_ROWB + (((unsigned)(16 * ni + 4 * tp) * 2) ^ (((rowi >> 3) & 1u) << 5));
         }
-
-    auto frag2 = [&](const unsigned char *lo, const unsigned char *hi) -> az_bf16x8 {  // k rows 0..3 at lo, 4..7 at hi
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(lo));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(hi));
-        s16x8 v;
-        v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
-        v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
-        return __builtin_bit_cast(az_bf16x8, v);
-    };
 
     const unsigned vb_c = (unsigned)a.CM * 4u, vb_f = (unsigned)a.CN * 4u;  // bytes per voxel
     const unsigned plane_c = (unsigned)a.H * a.W * vb_c, plane_f = (unsigned)a.H * a.W * vb_f;
@@ -164,30 +140,23 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
         auto commit_piece = [&](int it, int cbuf_idx, int frow0) {
             const int q = tid + 256 * it;
             uint2 hi, mid, lo;
-            if (AR) {
-                if (it == 0) az_stage_f16x4<(PSM & 1) != 0>(pre[it], c_scale, hi, mid);
-                else az_stage_f16x4<(PSM & 2) != 0>(pre[it], f_scale, hi, mid);
-                lo = mid;
-            } else {
-                az_split3_bf16x4(__builtin_bit_cast(float4, pre[it]), hi, mid, lo);
-            }
+            if (it == 0) az_wgrad_split<AR, (PSM & 1) != 0>(pre[it], c_scale, hi, mid, lo);
+            else az_wgrad_split<AR, (PSM & 2) != 0>(pre[it], f_scale, hi, mid, lo);
             unsigned char *dst;
             unsigned part_stride;
             if (it == 0) {
-                dst = cbuf + cbuf_idx * W16_CBUF + (q >> 3) * W16_ROWB + (((q & 7) * 8) ^ ((((q >> 3) >> 3) & 1) << 5));
+                dst = cbuf + cbuf_idx * W16_CBUF + az_w16_piece_off(q >> 3, q);
                 part_stride = 32 * W16_ROWB;
             } else {
                 const int f = q - 256;
                 const int kd = f / 288, g = f - kd * 288;
                 const int j = g / 144, pp = (g - j * 144) >> 3;
                 const int slot = (frow0 + j + W16_RING) % W16_RING;
-                dst = fring + (kd * W16_RING + slot) * W16_FROW + pp * W16_ROWB + (((q & 7) * 8) ^ (((pp >> 3) & 1) << 5));
+                dst = fring + (kd * W16_RING + slot) * W16_FROW + az_w16_piece_off(pp, q);
                 part_stride = W16_FW * W16_ROWB;
             }
             if (q >= W16_NQ) { dst = lds + W16_LDS + (tid & 7) * 8; part_stride = 0; }  // (no branch: a step stays one block)
-            *reinterpret_cast<uint2 *>(dst) = hi;
-            *reinterpret_cast<uint2 *>(dst + part_stride) = mid;
-            if (!AR) *reinterpret_cast<uint2 *>(dst + 2 * part_stride) = lo;
+            az_wgrad_store_parts<AR>(dst, part_stride, hi, mid, lo);
         };
 
         // ---- prologue: the window of step 0 (fine rows -1 .. 2, coarse rows 0, 1), then the request for step 1 -------
@@ -215,14 +184,14 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
 
             az_bf16x8 af[NP];
 #pragma unroll
-            for (int p = 0; p < NP; ++p) af[p] = frag2(ca + p * 32 * W16_ROWB, ca + p * 32 * W16_ROWB + 4 * W16_ROWB);
+            for (int p = 0; p < NP; ++p) af[p] = __builtin_bit_cast(az_bf16x8, az_tr16_frag(ca + p * 32 * W16_ROWB, ca + p * 32 * W16_ROWB + 4 * W16_ROWB));
             az_bf16x8 bf[2][NP];
             auto load_b = [&](az_bf16x8 (&bq)[NP], int t) {
                 const int kd = t / 9, kh = (t % 9) / 3, kw = t % 3;
                 const unsigned char *fp = fring + kd * (W16_RING * W16_FROW) + fb[kh];
 #pragma unroll
                 for (int p = 0; p < NP; ++p)
-                    bq[p] = frag2(fp + b_off[kw][0] + p * W16_FW * W16_ROWB, fp + b_off[kw][1] + p * W16_FW * W16_ROWB);
+                    bq[p] = __builtin_bit_cast(az_bf16x8, az_tr16_frag(fp + b_off[kw][0] + p * W16_FW * W16_ROWB, fp + b_off[kw][1] + p * W16_FW * W16_ROWB));
             };
             load_b(bf[0], 0);
 #pragma unroll
@@ -230,21 +199,7 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (t + 1 < 27) load_b(bf[(t + 1) & 1], t + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                f32x4 c = acc[t];
-                const az_bf16x8(&bq)[NP] = bf[t & 1];
-                if constexpr (AR) {  // lo*hi, hi*lo, hi*hi chained into the running accumulator (smallest first, as below)
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[1]), __builtin_bit_cast(az_f16x8, bq[0]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bq[1]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(az_f16x8, af[0]), __builtin_bit_cast(az_f16x8, bq[0]), c, 0, 0, 0);
-                } else {
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[2], bq[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[2], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1], bq[0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0], bq[0], c, 0, 0, 0);
-                }
-                acc[t] = c;
+                az_wgrad_chain<AR>(acc[t], af, bf[t & 1]);
                 // the set of step s+1 (requested a step ago): one piece after each of the taps 1, 3, 5, 7, 9; then the
                 // request for step s+2 (17 taps + the next step's first ones to land)
                 if (t >= 1 && t <= 9 && (t & 1)) {
@@ -259,7 +214,8 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
             __syncthreads();  // next step's rows written by all four waves; this step's no longer read
         }
     }
-    // D[i][j]: i = coarse channel 16 mi + 4 (lane >> 4) + r, j = fine channel 16 ni + (lane & 15)
+    // D[i][j]: i = coarse channel 16 mi + 4 (lane >> 4) + r, j = fine channel 16 ni + (lane & 15): az_wgrad_flush16 written out
+    // (called as a function it moves this kernel's registers as the lane geometry above does)
 #pragma unroll
     for (int t = 0; t < 27; ++t)
 #pragma unroll
@@ -298,10 +254,9 @@ int az_conv3d_wgrad_r16_launch(float *ws, const float *coarse, const float *fine
     if (!(coarse_amax && fine_amax)) {
         if (split_mask) return AZ_EINVAL;
         hipLaunchKernelGGL(conv3d_wgrad_r16_kernel<0>, grid, dim3(256), 0, s, a);
-    } else if (split_mask == 0) hipLaunchKernelGGL((conv3d_wgrad_r16_kernel<1, 0>), grid, dim3(256), 0, s, a);
-    else if (split_mask == 1) hipLaunchKernelGGL((conv3d_wgrad_r16_kernel<1, 1>), grid, dim3(256), 0, s, a);
-    else if (split_mask == 2) hipLaunchKernelGGL((conv3d_wgrad_r16_kernel<1, 2>), grid, dim3(256), 0, s, a);
-    else if (split_mask == 3) hipLaunchKernelGGL((conv3d_wgrad_r16_kernel<1, 3>), grid, dim3(256), 0, s, a);
-    else return AZ_EINVAL;
+    } else if (!az_wgrad_split_dispatch<3>(split_mask, [&](auto psm) {
+                   hipLaunchKernelGGL((conv3d_wgrad_r16_kernel<1, decltype(psm)::value>), grid, dim3(256), 0, s, a);
+               }))
+        return AZ_EINVAL;
     return az_launch_status();
 }

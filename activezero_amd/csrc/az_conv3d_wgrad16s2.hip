@@ -38,13 +38,8 @@
 // (((row + 1) >> 1) & 1) << 5), so the two octets always hit different halves of the bank period whatever the ring slots.
 #include <stdlib.h>
 
-#include "az_roll_common.h"
+#include "az_wgrad_common.h"
 #include "az_options.h"
-#include "az_launch_math.h"
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 
 #define S2_ROWB 64                                  // bytes of one (position, 32 channels) fp16 row
 #define S2_FPOS AZ_S2W_FPOS                                  // fine positions staged per row: odd image 9, even image 8
@@ -93,9 +88,8 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
     for (int t = 0; t < 7; ++t)
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) acc[t][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int kc = az_f16_scale_exp(az_amax_read(a.coarse_amax));
-    const int kf = az_f16_scale_exp(az_amax_read(a.fine_amax));
-    const float c_scale = az_pow2(kc), f_scale = az_pow2(kf), o_scale = ldexpf(1.f, -(kc + kf));
+    float c_scale, f_scale, o_scale;
+    az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
 
     // transposing-read geometry (ds_read_b64_tr_b16 on a [k][32 ch] image, az_conv3d_wgrad16.hip): a 16-lane group = one K
     // octet = one coarse row of the step; lane 4q + p supplies the address of k-row q (position q, then q + 4), channels
@@ -105,15 +99,6 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
     const unsigned a_lane = (unsigned)(8 * oct + tq) * S2_ROWB + (((unsigned)(4 * tp) * 2) ^ ((unsigned)(oct & 1) << 5));
     // fine: tap kw starts at LDS row 0 (odd image), 9 (even image), 1 (odd image, one further) of a staged row
     const unsigned b_lane = (unsigned)tq * S2_ROWB + (((unsigned)(16 * ni + 4 * tp) * 2) ^ ((unsigned)(oct & 1) << 5));
-
-    auto frag2 = [&](const unsigned char *lo, const unsigned char *hi) -> az_f16x8 {  // k rows 0..3 at lo, 4..7 at hi
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(lo));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(hi));
-        s16x8 v;
-        v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
-        v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
-        return __builtin_bit_cast(az_f16x8, v);
-    };
 
     const unsigned vb_c = 64u * 4u, vb_f = (unsigned)a.CN * 4u;  // bytes per voxel
     const unsigned plane_c = (unsigned)a.Hc * a.Wc * vb_c, plane_f = (unsigned)a.Hf * a.Wf * vb_f;
@@ -219,7 +204,7 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
                     const unsigned char *cm = cbuf + (s & 1) * S2_CBUF + (mb >> 1) * S2_CIMG + (a_lane ^ ((mb & 1) ? 32u : 0u)) + p * 2 * S2_CIMG;
-                    af[mb][p] = frag2(cm, cm + 4 * S2_ROWB);
+                    af[mb][p] = __builtin_bit_cast(az_f16x8, az_tr16_frag(cm, cm + 4 * S2_ROWB));
                 }
             az_f16x8 bf[2][2];
             auto load_b = [&](az_f16x8 (&bq)[2], int t) {
@@ -231,7 +216,8 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
                 unsigned off = (unsigned)v * S2_FROW + b_lane + (unsigned)(kd * (S2_RING * S2_FROW) + az_s2w_tap_row(kw) * S2_ROWB);
                 off ^= kh == 2 ? 32u : 0u;  // the row pair of kh = 2 is the next one: other half order
 #pragma unroll
-                for (int p = 0; p < 2; ++p) bq[p] = frag2(fring + off + p * S2_FPART, fring + off + 4 * S2_ROWB + p * S2_FPART);
+                for (int p = 0; p < 2; ++p)
+                    bq[p] = __builtin_bit_cast(az_f16x8, az_tr16_frag(fring + off + p * S2_FPART, fring + off + 4 * S2_ROWB + p * S2_FPART));
             };
             load_b(bf[0], 0);
 #pragma unroll
@@ -239,14 +225,7 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
                 __builtin_amdgcn_sched_barrier(0);
                 if (t + 1 < 7) load_b(bf[(t + 1) & 1], t + 1);
                 __builtin_amdgcn_sched_barrier(0);
-                const az_f16x8(&bq)[2] = bf[t & 1];
-                // four independent chains, each lo*hi, hi*lo, hi*hi into the running accumulator (smallest first)
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb) acc[t][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][1], bq[0], acc[t][mb], 0, 0, 0);
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb) acc[t][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][0], bq[1], acc[t][mb], 0, 0, 0);
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb) acc[t][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mb][0], bq[0], acc[t][mb], 0, 0, 0);
+                az_wgrad_chain4_f16x3(acc[t], af, bf[t & 1]);  // four independent chains (lo*hi, hi*lo, hi*hi), term by term
                 // the set of step s+1 (requested a step ago): two pieces behind each of four taps, and the request for the same
                 // two pieces of step s+2 as soon as their registers are free
                 if (t < 4) {
@@ -261,7 +240,8 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
             __syncthreads();  // next step's rows written by all eight waves; this step's no longer read
         }
     }
-    // D[i][j]: i = coarse channel 16 mb + 4 (lane >> 4) + r, j = fine channel 16 ni + (lane & 15)
+    // D[i][j]: i = coarse channel 16 mb + 4 (lane >> 4) + r, j = fine channel 16 ni + (lane & 15): az_wgrad_flush16 written out
+    // (called as a function it moves this kernel's spilled registers: 36 -> 34, or 37 for <2>, with the form of the call)
 #pragma unroll
     for (int t = 0; t < 7; ++t) {
         const int tap = tap0 + t;
@@ -290,9 +270,9 @@ int az_conv3d_wgrad_s2r16_launch(float *ws, const float *coarse, const float *fi
     a.ncols = (long long)B * Dc * a.nwchunk;
     a.wgs = az_wgrad16_workgroups(a.ncols, 256 / ntiles, ntiles, 0);
     const dim3 grid((unsigned)(a.wgs * ntiles));
-    if (split_mask == 0) hipLaunchKernelGGL(conv3d_wgrad_s2r16_kernel<0>, grid, dim3(512), 0, s, a);
-    else if (split_mask == 1) hipLaunchKernelGGL(conv3d_wgrad_s2r16_kernel<1>, grid, dim3(512), 0, s, a);
-    else if (split_mask == 2) hipLaunchKernelGGL(conv3d_wgrad_s2r16_kernel<2>, grid, dim3(512), 0, s, a);
-    else return AZ_EUNSUPPORTED;  // (both operands pre-split: no producer writes a pre-split forward activation yet)
+    if (!az_wgrad_split_dispatch<2>(split_mask, [&](auto psm) {
+            hipLaunchKernelGGL(conv3d_wgrad_s2r16_kernel<decltype(psm)::value>, grid, dim3(512), 0, s, a);
+        }))
+        return AZ_EUNSUPPORTED;  // (both operands pre-split: no producer writes a pre-split forward activation yet)
     return az_launch_status();
 }

@@ -151,6 +151,41 @@ inline int az_wgrad16_workgroups(long long ncols, int slots, int ntiles, int cap
     return best;
 }
 
+// C layout of the two MFMA shapes the weight-gradient kernels flush (az_wgrad_common.h): register `reg` of lane `lane` holds
+// element (row, col) of the tile -- 32x32: 16 registers, 16x16: 4 registers.
+AZ_HD int az_mfma32_c_row(int lane, int reg) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+AZ_HD int az_mfma32_c_col(int lane) { return lane & 31; }
+AZ_HD int az_mfma16_c_row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
+AZ_HD int az_mfma16_c_col(int lane) { return lane & 15; }
+
+// The r16 weight-gradient kernels' LDS images: [k row][32 channels] of 16-bit values, 64-byte rows = 16 banks, so rows r and
+// r + 8 fall on the same banks -- and the two octets of a 32-lane half of a transposing read address exactly such rows (a
+// 2-way conflict on every read, measured: 46 % of the LDS cycles).  The two 32-byte channel halves of a row are therefore
+// swapped on rows with bit 3 set: writes and reads XOR the in-row byte offset with az_w16_half_swap(row).
+#define AZ_W16_ROWB 64
+AZ_HD unsigned az_w16_half_swap(unsigned row) { return ((row >> 3) & 1u) << 5; }
+// staging: byte offset of the 8-byte piece q & 7 (channels 4 (q & 7) ..) of row `row`; q: the float4 piece index of the staging loops
+AZ_HD int az_w16_piece_off(int row, int q) { return row * AZ_W16_ROWB + (((q & 7) * 8) ^ (((row >> 3) & 1) << 5)); }
+// reading: the address lane 4q + p of a 16-lane group supplies for rows row0 .. row0 + 3 of the channel block from ch0 (0 or
+// 16): row row0 + q, channels ch0 + 4p ..
+AZ_HD unsigned az_w16_read_off(int lane, unsigned row0, unsigned ch0) {
+    const unsigned row = row0 + ((unsigned)(lane & 15) >> 2);
+    return row * AZ_W16_ROWB + (((ch0 + 4 * (unsigned)(lane & 3)) * 2) ^ az_w16_half_swap(row));
+}
+// Lane geometry of a K = 32 step = two coarse rows x 16 positions: octet oct = lane >> 4 holds k rows 8 oct ..; of the fine
+// window it reads row-of-the-pair rp = oct >> 1, positions 8 (oct & 1) .. shifted by the tap's kw (+ 4: the second half of a
+// fragment).  a_ch0 / b_ch0: the wave's 16-channel block inside the coarse / fine 32-channel image.
+struct AzW16Lanes { unsigned a_lane, b_off[3][2]; int rp; };
+AZ_HD AzW16Lanes az_w16_lanes(int lane, unsigned a_ch0, unsigned b_ch0) {
+    const unsigned oct = (unsigned)lane >> 4;
+    AzW16Lanes g;
+    g.a_lane = az_w16_read_off(lane, 8 * oct, a_ch0);
+    g.rp = (int)(oct >> 1);
+    for (int kw = 0; kw < 3; ++kw)
+        for (int h2 = 0; h2 < 2; ++h2) g.b_off[kw][h2] = az_w16_read_off(lane, 8 * (oct & 1) + kw + 4 * h2, b_ch0);
+    return g;
+}
+
 // az_conv2d_wgrad16.hip (3x3 d1 2-D weight gradient, 32 / 64 channels): a column of work = (image, 16-position chunk, row
 // segment); `slots` = workgroups resident per (co, ci) tile (768 / ntiles at three per CU; 256 for the one-tile-per-workgroup
 // 64 x 64 kernel).  Row segments have EVEN row counts (a step multiplies a pair of dy rows): of the up to 16 splits the one

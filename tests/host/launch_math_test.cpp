@@ -319,6 +319,58 @@ int main() {
             CHECK(visited == nt, "c1 wgrad: %lld of %lld items visited", visited, nt);
         }
     }
+    // C layout of the two MFMA shapes the weight-gradient kernels flush: every (lane, register) is a distinct (m, n), all of the tile
+    {
+        std::vector<char> seen32(32 * 32, 0), seen16(16 * 16, 0);
+        for (int lane = 0; lane < 64; ++lane) {
+            for (int rg = 0; rg < 16; ++rg) {
+                const int m = az_mfma32_c_row(lane, rg), n = az_mfma32_c_col(lane);
+                CHECK(m >= 0 && m < 32 && n >= 0 && n < 32, "32x32 C: lane %d reg %d -> (%d, %d)", lane, rg, m, n);
+                if (m >= 0 && m < 32 && n >= 0 && n < 32) { CHECK(!seen32[m * 32 + n], "32x32 C: (%d, %d) twice", m, n); seen32[m * 32 + n] = 1; }
+            }
+            for (int r = 0; r < 4; ++r) {
+                const int m = az_mfma16_c_row(lane, r), n = az_mfma16_c_col(lane);
+                CHECK(m >= 0 && m < 16 && n >= 0 && n < 16, "16x16 C: lane %d reg %d -> (%d, %d)", lane, r, m, n);
+                if (m >= 0 && m < 16 && n >= 0 && n < 16) { CHECK(!seen16[m * 16 + n], "16x16 C: (%d, %d) twice", m, n); seen16[m * 16 + n] = 1; }
+            }
+        }
+        for (int i = 0; i < 32 * 32; ++i) CHECK(seen32[i], "32x32 C: element %d never held", i);
+        for (int i = 0; i < 16 * 16; ++i) CHECK(seen16[i], "16x16 C: element %d never held", i);
+    }
+    // The row-half swap of the r16 weight-gradient images: what staging writes for (k row, channel) is what the transposing read
+    // of that (k row, channel) addresses, and the two octets of a 32-lane half read different 32-byte halves of the bank period.
+    {
+        for (int ch0 = 0; ch0 <= 16; ch0 += 16)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int oct = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
+                const AzW16Lanes g = az_w16_lanes(lane, ch0, ch0);
+                // coarse: k row 8 oct + tq (+ 4 for the second half of a fragment); the piece of channels ch0 + 4 tp ..
+                CHECK((int)g.a_lane == az_w16_piece_off(8 * oct + tq, (ch0 + 4 * tp) / 4), "a_lane of lane %d", lane);
+                CHECK(az_w16_piece_off(8 * oct + tq + 4, (ch0 + 4 * tp) / 4) == (int)g.a_lane + 4 * AZ_W16_ROWB, "a_lane + 4 rows, lane %d", lane);
+                CHECK(g.rp == (oct >> 1), "rp of lane %d", lane);
+                for (int kw = 0; kw < 3; ++kw)
+                    for (int h2 = 0; h2 < 2; ++h2) {
+                        const int row = 8 * (oct & 1) + tq + kw + 4 * h2;  // position + tap shift inside the 18-position row
+                        CHECK(row < 18, "fine row %d of lane %d", row, lane);
+                        CHECK((int)g.b_off[kw][h2] == az_w16_piece_off(row, (ch0 + 4 * tp) / 4), "b_off[%d][%d] of lane %d", kw, h2, lane);
+                    }
+                if (!(oct & 1)) {  // the other octet of this 32-lane half: same tq, tp
+                    const AzW16Lanes o = az_w16_lanes(lane + 16, ch0, ch0);
+                    CHECK(((g.a_lane ^ o.a_lane) & 32u) != 0, "a: octets of lane %d share a half", lane);
+                    for (int kw = 0; kw < 3; ++kw)
+                        for (int h2 = 0; h2 < 2; ++h2)
+                            CHECK(((g.b_off[kw][h2] ^ o.b_off[kw][h2]) & 32u) != 0, "b[%d][%d]: octets of lane %d share a half", kw, h2, lane);
+                }
+            }
+        // staging covers every 8-byte piece of a 32-row image exactly once
+        std::vector<char> seen(32 * AZ_W16_ROWB / 8, 0);
+        for (int row = 0; row < 32; ++row)
+            for (int q = 0; q < 8; ++q) {
+                const int off = az_w16_piece_off(row, q);
+                CHECK(off >= 0 && off < 32 * AZ_W16_ROWB && off % 8 == 0 && off / AZ_W16_ROWB == row && !seen[off / 8], "piece (%d, %d) -> %d", row, q, off);
+                if (off >= 0 && off < 32 * AZ_W16_ROWB) seen[off / 8] = 1;
+            }
+    }
     std::printf("launch math: %d failures\n", fails);
     return fails ? 1 : 0;
 }
