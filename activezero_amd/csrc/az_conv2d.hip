@@ -26,6 +26,7 @@
 // eval-mode caller folds BatchNorm here.  Output pixel stride is a parameter, so a producer can write
 // straight into a channel slice of a wider tensor.
 #include "az_pack_f16.h"
+#include "az_gather_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -33,7 +34,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define C2_TY 8
 #define C2_TX 16
 #define C2_PITCH 20  // LDS row pitch in pixels (== 4 mod 8: az_conv3d_m128.hip)
-#define C2_VS 24     // dwords per slab pixel: 3 parts x 16 ch bf16
+#define C2_VS AZ_S24_VS  // dwords per slab pixel: 3 parts x 16 ch bf16
 
 struct C2Args {
     const float *in;   // [B,H,W,*] pixel stride in_cs floats, channels [0, cin) used
@@ -69,6 +70,7 @@ __global__ void __launch_bounds__(64 * NW, 2)
 conv2d_same_kernel(const C2Args a) {
     static_assert(!H1 || PARTS == 1, "H1 is the fp16 form of the one-part arithmetic");
     constexpr int T = KH * KW;
+    constexpr int AR = PARTS == 3 ? 0 : PARTS == 2 ? 1 : H1 ? 3 : 2;  // the slab image's arithmetic (az_gather_common.h)
     constexpr int HY = DIL * (KH - 1) / 2, HX = DIL * (KW - 1) / 2;
     constexpr int SY = C2_TY + 2 * HY, SX = C2_TX + 2 * HX;
     static_assert(SX <= C2_PITCH, "slab row does not fit the LDS pitch");
@@ -85,11 +87,7 @@ conv2d_same_kernel(const C2Args a) {
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // ---- block -> (cout group, patch): XCD-chunked linear order, cout groups of a patch adjacent ----
-    int lin = blockIdx.x;
-    {
-        const int nblk = gridDim.x, xcd = blockIdx.x & 7, q8 = nblk >> 3, r8 = nblk & 7;
-        lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    }
+    int lin = az_xcd_map(blockIdx.x, gridDim.x);
     const int grp = lin % a.ngroups; lin /= a.ngroups;
     const int tix = lin % a.tiles_x; lin /= a.tiles_x;
     const int tiy = lin % a.tiles_y;
@@ -105,18 +103,8 @@ conv2d_same_kernel(const C2Args a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
     float in_scale = 1.f, osc = 1.f;
-    if (PARTS == 2) {  // wave-uniform power-of-two operand scales
-        const int ki = az_f16_scale_exp(az_amax_read(a.in_amax));
-        const int kw_ = az_f16_scale_exp(az_amax_read(a.w_amax));
-        in_scale = az_pow2(ki);
-        osc = ldexpf(1.f, -(ki + kw_));
-    }
-    if (H1) {  // (either amax may be absent: that operand is rounded as it is, the way autocast does)
-        const int ki = a.in_amax ? az_f16_scale_exp(az_amax_read(a.in_amax)) : 0;
-        const int kw_ = a.w_amax ? az_f16_scale_exp(az_amax_read(a.w_amax)) : 0;
-        in_scale = az_pow2(ki);
-        osc = ldexpf(1.f, -(ki + kw_));
-    }
+    if (PARTS == 2) az_f16_scales(a.in_amax, a.w_amax, in_scale, osc);
+    if (H1) az_f16_scales<true>(a.in_amax, a.w_amax, in_scale, osc);  // (an absent amax: that operand is rounded as it is, the way autocast does)
 
     const int row = lane & 31, half = lane >> 5;
     const int rty = row >> 3, rtx = row & 7;
@@ -147,26 +135,7 @@ conv2d_same_kernel(const C2Args a) {
             const int q = tid + NTHR * it, pix = q >> 2, j = q & 3;
             const int sy = pix / SX, sx = pix - sy * SX;
             if (!((okbits >> it) & 1u)) pre[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q < NQ) {
-                unsigned *dst = sb + (sy * C2_PITCH + sx) * C2_VS + (((j >> 1) ^ (sy & 1)) * 4) + (j & 1) * 2;
-                if (PARTS == 3) {
-                    uint2 hi, mid, lo;
-                    az_split3_bf16x4(pre[it], hi, mid, lo);
-                    *reinterpret_cast<uint2 *>(dst) = hi;
-                    *reinterpret_cast<uint2 *>(dst + 8) = mid;
-                    *reinterpret_cast<uint2 *>(dst + 16) = lo;
-                } else if (PARTS == 2) {
-                    uint2 hi, lo;
-                    az_split2_f16x4(make_float4(pre[it].x * in_scale, pre[it].y * in_scale, pre[it].z * in_scale, pre[it].w * in_scale), hi, lo);
-                    *reinterpret_cast<uint2 *>(dst) = hi;
-                    *reinterpret_cast<uint2 *>(dst + 8) = lo;
-                } else if (H1) {
-                    *reinterpret_cast<uint2 *>(dst) = make_uint2(az_pk_f16(pre[it].x * in_scale, pre[it].y * in_scale),
-                                                                 az_pk_f16(pre[it].z * in_scale, pre[it].w * in_scale));
-                } else {
-                    *reinterpret_cast<uint2 *>(dst) = make_uint2(az_pk_bf16(pre[it].x, pre[it].y), az_pk_bf16(pre[it].z, pre[it].w));
-                }
-            }
+            if (q < NQ) az_s24_commit<AR>(sb, sy, sx, j, C2_PITCH, pre[it], in_scale);
         }
     };
     // packed weights: [tap][chunk][ntile][part][lane] float4
@@ -177,12 +146,10 @@ conv2d_same_kernel(const C2Args a) {
     };
     // A fragments: two per-lane bases (row parity decides the half swap), compile-time offsets otherwise
     const float *abase[2];
-    abase[0] = &slab[(rty * C2_PITCH + rtx) * C2_VS + ((half ^ (rty & 1)) * 4)];
-    abase[1] = &slab[(rty * C2_PITCH + rtx) * C2_VS + ((half ^ ((rty + 1) & 1)) * 4)];
+    abase[0] = &slab[az_s24_read_base(rty, rtx, half, 0, C2_PITCH)];
+    abase[1] = &slab[az_s24_read_base(rty, rtx, half, 1, C2_PITCH)];
     auto load_a = [&](float4 (&aq)[3], int buf, int m, int oy, int ox) {
-        const float *ap = abase[oy & 1] + buf * SLAB + ((4 * (m >> 1) + oy) * C2_PITCH + 8 * (m & 1) + ox) * C2_VS;
-#pragma unroll
-        for (int p = 0; p < PARTS; ++p) aq[p] = *reinterpret_cast<const float4 *>(ap + 8 * p);
+        az_s24_load<PARTS>(aq, abase[oy & 1] + buf * SLAB + ((4 * (m >> 1) + oy) * C2_PITCH + 8 * (m & 1) + ox) * C2_VS);
     };
     // block products are summed in two alternating temporaries; the accumulators take each finished
     // temporary one block later (az_common.h az_mfma6_step): acc[3] of a tap is completed under the next
@@ -337,6 +304,7 @@ conv2d_same_kernel(const C2Args a) {
     if constexpr (STATS) {
         // BatchNorm partials of this wave's 32 channels over the patch (the layer's BatchNorm then skips its own
         // statistics pass over the tensor): lane = channel co, its 64 values + the other half-wave's 64
+        // (not az_tile_moments: this block adds its squares with fmaf under a predicate, that one a rounded product under a mask)
         float sm = 0.f;
         int n = 0;
 #pragma unroll

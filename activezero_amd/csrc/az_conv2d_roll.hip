@@ -48,11 +48,7 @@ conv2d_roll_kernel(const C2RArgs a) {
     constexpr int NP = AR ? 2 : 3;
     constexpr int TAPF4 = NCH * 2 * NP * 64;  // float4 per tap of one channel group: [tap][cc][n16][part][lane]
     float in_scale = 1.f, osc = 1.f;
-    if (AR) {
-        const int ki = az_f16_scale_exp(az_amax_read(a.in_amax)), kw_ = az_f16_scale_exp(az_amax_read(a.w_amax));
-        in_scale = az_pow2(ki);
-        osc = ldexpf(1.f, -(ki + kw_));
-    }
+    if (AR) az_f16_scales(a.in_amax, a.w_amax, in_scale, osc);
     __shared__ __attribute__((aligned(16))) unsigned char slab[2 * R_SLAB_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -323,8 +319,8 @@ __global__ void __launch_bounds__(256, 2)
 conv2d_roll64_kernel(const C2RArgs a) {
     constexpr int NCH = CIN / 32;
     constexpr int TAPF4 = NCH * 2 * 2 * 64;  // float4 per tap of one 32-channel group: [tap][cc][n16][part][lane]
-    const int ki = az_f16_scale_exp(az_amax_read(a.in_amax)), kw_ = az_f16_scale_exp(az_amax_read(a.w_amax));
-    const float in_scale = az_pow2(ki), osc = ldexpf(1.f, -(ki + kw_));
+    float in_scale, osc;
+    az_f16_scales(a.in_amax, a.w_amax, in_scale, osc);
     __shared__ __attribute__((aligned(16))) unsigned char slab[2 * R_SLAB_BYTES];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);

@@ -47,8 +47,8 @@ conv2d_wgrad_kernel(const W2Args a) {
     // power of two from an amax array (null = scale 1)
     constexpr int NP = (AR == 2 || AR == 3) ? 1 : AR ? 2 : 3;
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR == 1) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
-    if (AR == 3) az_wgrad_scales<true>(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
+    if (AR == 1) az_f16_scales(a.coarse_amax, a.fine_amax, c_scale, o_scale, &f_scale);
+    if (AR == 3) az_f16_scales<true>(a.coarse_amax, a.fine_amax, c_scale, o_scale, &f_scale);
     constexpr int CY = (KH - 1) / 2, CX = (KW - 1) / 2;
     constexpr int WCH = W2_WCH;
     constexpr int FW = WCH + (KW - 1) * DIL;       // fine positions per staged row

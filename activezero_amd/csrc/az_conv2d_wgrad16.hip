@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256, 3)
 conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
     constexpr int NP = AR ? 2 : 3;
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
+    if (AR) az_f16_scales(a.coarse_amax, a.fine_amax, c_scale, o_scale, &f_scale);
     __shared__ __attribute__((aligned(16))) unsigned char lds[V16_LDS + 64];  // + a sink for the lanes of a partial piece
     unsigned char *const cbuf = lds;                  // [2][V16_CBUF]
     unsigned char *const fring = lds + 2 * V16_CBUF;  // [slot][V16_FROW]
@@ -211,7 +211,7 @@ conv2d_wgrad_r16_kernel(const Wg2dArgs a) {
 __global__ void __launch_bounds__(512, 1)
 conv2d_wgrad_w64_kernel(const Wg2dArgs a) {
     float c_scale, f_scale, o_scale;
-    az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
+    az_f16_scales(a.coarse_amax, a.fine_amax, c_scale, o_scale, &f_scale);
     __shared__ __attribute__((aligned(16))) unsigned char lds[X16_LDS + 64];  // + a sink for the lanes of the partial piece
     unsigned char *const cbuf = lds;                  // [2][X16_CBUF]
     unsigned char *const fring = lds + 2 * X16_CBUF;  // [slot][X16_FROW]

@@ -31,9 +31,8 @@
 // feature maps (reference psmnet_3.py:149-163) instead of reading a 64-channel tensor.
 #include <stdlib.h>
 
-#include "az_roll_common.h"
+#include "az_gather_common.h"
 #include "az_options.h"
-#include "az_launch_math.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -106,35 +105,15 @@ conv3d_gather_kernel(const ConvArgs a) {
     // (2) banded order inside the chunk: x fastest, then CV_BAND tile rows, then the depth
     //     index, then the band -- so the three output planes that read one input plane
     //     (and the row halos inside a band) are processed back to back and hit in L2.
-    // Pure performance choice; any map that is a bijection onto the tile set is correct.
-    int lin = blockIdx.x;
-    if (a.map_mode >= 1) {
-        const int nblk = gridDim.x, xcd = blockIdx.x & 7, q8 = nblk >> 3, r8 = nblk & 7;
-        lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    }
+    // Pure performance choice; any map that is a bijection onto the tile set is correct (az_launch_math.h).
+    int lin = a.map_mode >= 1 ? az_xcd_map(blockIdx.x, gridDim.x) : blockIdx.x;
     int pd = 0, ph = 0, pw = 0;
     if (MODE == 2) {
         const int phase = lin & 7; lin >>= 3;
         pd = phase >> 2; ph = (phase >> 1) & 1; pw = phase & 1;
     }
-    const int tix = lin % a.tiles_x; lin /= a.tiles_x;
-    int tiy, td, b;
-    if (a.map_mode >= 2) {
-        // lin indexes (b, band, d, row-in-band); the last band may have fewer rows
-        const int per_b = a.Dt * a.tiles_y;
-        b = lin / per_b;
-        int l = lin - b * per_b;
-        const int full = (a.tiles_y / CV_BAND) * CV_BAND * a.Dt;  // blocks in the complete bands
-        int band, rows;
-        if (l < full) { band = l / (CV_BAND * a.Dt); l -= band * CV_BAND * a.Dt; rows = CV_BAND; }
-        else { band = a.tiles_y / CV_BAND; l -= full; rows = a.tiles_y - band * CV_BAND; }
-        td = l / rows;
-        tiy = band * CV_BAND + (l - td * rows);
-    } else {
-        tiy = lin % a.tiles_y; lin /= a.tiles_y;
-        td = lin % a.Dt;
-        b = lin / a.Dt;
-    }
+    int tix, tiy, td, b;
+    az_conv_tile_decode(lin, a.map_mode, CV_BAND, a.tiles_x, a.tiles_y, a.Dt, tix, tiy, td, b);
     // canonical tile id (rows of the BatchNorm partial buffers)
     const int tile_id = ((((b * a.Dt + td) * a.tiles_y + tiy) * a.tiles_x + tix) << (MODE == 2 ? 3 : 0)) +
                         (MODE == 2 ? (pd * 4 + ph * 2 + pw) : 0);
@@ -152,12 +131,7 @@ conv3d_gather_kernel(const ConvArgs a) {
             for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
 
     float in_scale = 1.f, osc = 1.f;
-    if (X16) {  // wave-uniform power-of-two operand scales from the tensors' largest magnitudes
-        const int ki = az_f16_scale_exp(az_amax_read(a.in_amax));
-        const int kw = az_f16_scale_exp(az_amax_read(a.w_amax));
-        in_scale = az_pow2(ki);
-        osc = ldexpf(1.f, -(ki + kw));
-    }
+    if (X16) az_f16_scales(a.in_amax, a.w_amax, in_scale, osc);
     const int nd = (MODE == 2) ? 1 + pd : 3;
     const int nh = (MODE == 2) ? 1 + ph : 3;
     const int nw = (MODE == 2) ? 1 + pw : 3;
@@ -418,8 +392,7 @@ conv3d_gather_kernel(const ConvArgs a) {
             for (int n = 0; n < NR; ++n) acc[m][n] *= osc;
     }
     // ---- epilogue ---------------------------------------------------------------------
-    // C/D map of 32x32 MFMA: column (out channel) = lane & 31, row (voxel) =
-    // (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
+    // C/D map of 32x32 MFMA: column (out channel) = lane & 31, row (voxel) = az_mfma32_c_row.
     const int od = (MODE == 2) ? 2 * td + pd : td;
     // Addresses: wave-uniform 64-bit plane base + 32-bit offsets.  A tile that lies completely
     // inside the output (every interior tile) takes the branch-free path.
@@ -434,7 +407,7 @@ conv3d_gather_kernel(const ConvArgs a) {
     const bool full = (oh_base + ohs * (TY - 1) < a.Ho) && (ow_base + ohs * (TX - 1) < a.Wo);
     // offset (in floats) of accumulator register r of M-tile m, and its validity
     auto voxel = [&](int m, int r, unsigned &off) -> bool {
-        const int vrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int vrow = az_mfma32_c_row_h(half, r);
         const int oh = oh_base + ohs * (vrow >> 3), ow = ow_base + ohs * ((vrow & 7) + 8 * m);
         off = (unsigned)(oh * a.Wo + ow) * COUT + row;
         return full || ((oh < a.Ho) && (ow < a.Wo));
@@ -453,12 +426,7 @@ conv3d_gather_kernel(const ConvArgs a) {
                 unsigned off;
                 if (!voxel(m, r, off)) continue;
 #pragma unroll
-                for (int n = 0; n < NR; ++n) {
-                    float y = acc[qb + m][n][r] * sc[n] + sf[n];
-                    if (resp) y += resp[off + n * 32];
-                    if (a.relu) y = fmaxf(y, 0.f);
-                    outp[off + n * 32] = y;
-                }
+                for (int n = 0; n < NR; ++n) az_store_affine(outp, resp, off + n * 32, acc[qb + m][n][r], sc[n], sf[n], a.relu);
             }
     } else {
         int nvalid = 0;
@@ -476,46 +444,14 @@ conv3d_gather_kernel(const ConvArgs a) {
                     for (int n = 0; n < NR; ++n) outp[off + n * 32] = acc[qb + m][n][r];
                 }
             }
-        const int ntot = nvalid + __shfl_xor(nvalid, 32);
 #pragma unroll
         for (int n = 0; n < NR; ++n) {
-            float s = 0.f, m2 = 0.f;
-            if (full) {  // wave-uniform: no masking
-#pragma unroll
-                for (int m = 0; m < MR; ++m)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s += acc[qb + m][n][r];
-                s += __shfl_xor(s, 32);
-                const float mean = s / (float)(MR * 32);
-#pragma unroll
-                for (int m = 0; m < MR; ++m)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float dlt = acc[qb + m][n][r] - mean;
-                        m2 += dlt * dlt;
-                    }
-            } else {
-#pragma unroll
-                for (int m = 0; m < MR; ++m)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s += ((okmask >> (m * 16 + r)) & 1u) ? acc[qb + m][n][r] : 0.f;
-                s += __shfl_xor(s, 32);
-                const float mean = s / (float)max(ntot, 1);
-#pragma unroll
-                for (int m = 0; m < MR; ++m)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float dlt = acc[qb + m][n][r] - mean;
-                        m2 += ((okmask >> (m * 16 + r)) & 1u) ? dlt * dlt : 0.f;
-                    }
-            }
-            m2 += __shfl_xor(m2, 32);
-            if (half == 0) {
-                const int co = n * 32 + row;
-                *reinterpret_cast<float2 *>(&a.part[((size_t)co * a.ntiles + tile_q) * 2]) = make_float2(s, m2);
-            }
+            auto get = [&](int m, int r) { return acc[qb + m][n][r]; };
+            float s, m2;
+            const int ntot = full ? az_tile_moments<MR, true>(okmask, nvalid, get, s, m2)  // wave-uniform: no masking
+                                  : az_tile_moments<MR, false>(okmask, nvalid, get, s, m2);
+            az_tile_moments_store(a.part, a.cnt, a.ntiles, n * 32 + row, tile_q, half, s, m2, ntot);
         }
-        if (lane == 0) a.cnt[tile_q] = (float)ntot;
     }
     }  // phases
     CV_ACC(4);
@@ -541,17 +477,22 @@ conv3d_pack_kernel(float *__restrict__ dst, const float *__restrict__ src, int c
     dst[idx] = src[co * sn + ci * sk + (flip ? 26 - tap : tap)];
 }
 
-// bf16x6 packing: [tap][cc][n][part(3)][kb(2)][lane(64)][8] bf16, element j of lane =
-// part `p` of src(co = n*32 + (lane&31), ci = cc*32 + 16*kb + 8*(lane>>5) + j, tap)
+// bf16x6 / f16x3 packing: [tap][cc][n][part(3 / 2)][kb(2)][lane(64)][8] 16-bit values, element j of lane = part `p` of
+// src(co = n*32 + (lane&31), ci = cc*32 + 16*kb + 8*(lane>>5) + j, tap): the round-to-nearest bf16 split, as the
+// activations' (az_common.h), or (F16) the fp16 split of w * 2^k, k from max |w|
+template <bool F16>
 __global__ void __launch_bounds__(256)
-conv3d_pack_x6_kernel(unsigned short *__restrict__ dst, const float *__restrict__ src, int cin,
-                      int cout, long long sn, long long sk, int flip, int total) {
+conv3d_pack_parts_kernel(unsigned short *__restrict__ dst, const float *__restrict__ src, const float *__restrict__ amax,
+                         int cin, int cout, long long sn, long long sk, int flip, int total) {
+    constexpr int NP = F16 ? 2 : 3;
     const int idx = blockIdx.x * 256 + threadIdx.x;
+    float scale = 1.f;
+    if (F16) scale = az_pow2(az_f16_scale_exp(az_amax_read(amax)));  // (before the early exit: a wave-wide read)
     if (idx >= total) return;
     const int j = idx & 7, lane = (idx >> 3) & 63;
     int r = idx >> 9;
     const int kb = r & 1; r >>= 1;
-    const int p = r % 3; r /= 3;
+    const int p = r % NP; r /= NP;
     const int nr = cout / 32, nch = cin / 32;
     const int n = r % nr; r /= nr;
     const int cc = r % nch;
@@ -559,27 +500,7 @@ conv3d_pack_x6_kernel(unsigned short *__restrict__ dst, const float *__restrict_
     const int co = n * 32 + (lane & 31);
     const int ci = cc * 32 + 16 * kb + 8 * (lane >> 5) + j;
     const float x = src[co * sn + ci * sk + (flip ? 26 - tap : tap)];
-    dst[idx] = az_split3_part(x, p);  // round-to-nearest split, as the activations' (az_common.h)
-}
-
-// f16x3 packing for this kernel: [tap][cc][n][part(2)][kb(2)][lane(64)][8] fp16 of w * 2^k (k from max |w|)
-__global__ void __launch_bounds__(256)
-conv3d_pack_f16_kernel(unsigned short *__restrict__ dst, const float *__restrict__ src, const float *__restrict__ amax,
-                       int cin, int cout, long long sn, long long sk, int flip, int total) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    const float scale = az_pow2(az_f16_scale_exp(az_amax_read(amax)));  // (before the early exit: a wave-wide read)
-    if (idx >= total) return;
-    const int j = idx & 7, lane = (idx >> 3) & 63;
-    int r = idx >> 9;
-    const int kb = r & 1; r >>= 1;
-    const int p = r & 1; r >>= 1;
-    const int nr = cout / 32, nch = cin / 32;
-    const int n = r % nr; r /= nr;
-    const int cc = r % nch;
-    const int tap = r / nch;
-    const int co = n * 32 + (lane & 31);
-    const int ci = cc * 32 + 16 * kb + 8 * (lane >> 5) + j;
-    dst[idx] = az_split2_f16_part(src[co * sn + ci * sk + (flip ? 26 - tap : tap)] * scale, p);
+    dst[idx] = F16 ? az_split2_f16_part(x * scale, p) : az_split3_part(x, p);
 }
 
 template <int CIN, int COUT, int MODE, int EPI, int SRC, int PREC>
@@ -613,25 +534,20 @@ static int dispatch_channels(const ConvArgs &a, int cin, int cout, int src, hipS
     return AZ_EUNSUPPORTED;
 }
 
+template <int EPI, int PREC>
+static int dispatch_map(const ConvArgs &a, int mode, int cin, int cout, int src, hipStream_t s) {
+    if (mode == 0) return dispatch_channels<0, EPI, PREC>(a, cin, cout, src, s);
+    if (mode == 1) return dispatch_channels<1, EPI, PREC>(a, cin, cout, src, s);
+    return dispatch_channels<2, EPI, PREC>(a, cin, cout, src, s);
+}
+
 template <int EPI>
 static int dispatch_mode(const ConvArgs &a, int mode, int precision, int cin, int cout, int src,
                          hipStream_t s) {
-    if (precision == 0) {
-        if (mode == 0) return dispatch_channels<0, EPI, 0>(a, cin, cout, src, s);
-        if (mode == 1) return dispatch_channels<1, EPI, 0>(a, cin, cout, src, s);
-        return dispatch_channels<2, EPI, 0>(a, cin, cout, src, s);
-    }
-    if (precision == 1) {
-        if (mode == 0) return dispatch_channels<0, EPI, 1>(a, cin, cout, src, s);
-        if (mode == 1) return dispatch_channels<1, EPI, 1>(a, cin, cout, src, s);
-        return dispatch_channels<2, EPI, 1>(a, cin, cout, src, s);
-    }
-    if (precision == 3) {  // f16x3 on this kernel (shapes the depth-rolling kernel does not take)
-        if (src != 0) return AZ_EUNSUPPORTED;
-        if (mode == 0) return dispatch_channels<0, EPI, 3>(a, cin, cout, src, s);
-        if (mode == 1) return dispatch_channels<1, EPI, 3>(a, cin, cout, src, s);
-        return dispatch_channels<2, EPI, 3>(a, cin, cout, src, s);
-    }
+    if (precision == 0) return dispatch_map<EPI, 0>(a, mode, cin, cout, src, s);
+    if (precision == 1) return dispatch_map<EPI, 1>(a, mode, cin, cout, src, s);
+    if (precision == 3)  // f16x3 on this kernel (shapes the depth-rolling kernel does not take)
+        return src != 0 ? AZ_EUNSUPPORTED : dispatch_map<EPI, 3>(a, mode, cin, cout, src, s);
     if (precision == 2) {  // bf16x6 arithmetic, weights packed for the depth-rolling 16x16x32 kernel
         if (mode != 0 || cout != 32 || src != 0) return AZ_EUNSUPPORTED;
         return az_conv3d_roll_launch(a, cin, EPI, s);
@@ -686,8 +602,8 @@ extern "C" int az_conv3d_pack_weights(float *packed, const float *w, int cin, in
                            az_stream(stream), packed, w, cin, cout, stride_out, stride_in, flip, total);
     } else if (precision == 1) {
         const int total = 27 * cin * cout * 3;
-        hipLaunchKernelGGL(conv3d_pack_x6_kernel, dim3((total + 255) / 256), dim3(256), 0,
-                           az_stream(stream), reinterpret_cast<unsigned short *>(packed), w, cin, cout,
+        hipLaunchKernelGGL(conv3d_pack_parts_kernel<false>, dim3((total + 255) / 256), dim3(256), 0,
+                           az_stream(stream), reinterpret_cast<unsigned short *>(packed), w, nullptr, cin, cout,
                            stride_out, stride_in, flip, total);
     } else if (precision == 2) {
         return az_conv3d_pack_r16(packed, w, cin, cout, stride_out, stride_in, flip, az_stream(stream));
@@ -699,13 +615,12 @@ extern "C" int az_conv3d_pack_weights(float *packed, const float *w, int cin, in
 
 static int conv_map_mode() { return az_options().conv_map; }
 
-static int conv_common(ConvArgs &a, int mode, int B, int cin, int Di, int Hi, int Wi, int src) {
+static int conv_common(ConvArgs &a, int mode, int B, int Di, int Hi, int Wi) {
     if (mode < 0 || mode > 2 || B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0) return AZ_EINVAL;
     a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi;
     a.map_mode = conv_map_mode();
     conv_out_dims(mode, Di, Hi, Wi, a.Do, a.Ho, a.Wo);
     conv_tiles(mode, Di, Hi, Wi, a.Dt, a.tiles_y, a.tiles_x);
-    (void)cin; (void)src;
     return AZ_OK;
 }
 
@@ -716,10 +631,18 @@ extern "C" int az_conv3d_fwd(float *out, const float *in, const float *in2,
     AZ_REQUIRE_PTR(out); AZ_REQUIRE_PTR(in); AZ_REQUIRE_PTR(packed_w);
     if (src == 1) AZ_REQUIRE_PTR(in2);
     ConvArgs a{};
-    if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, src)) return e;
+    if (int e = conv_common(a, mode, B, Di, Hi, Wi)) return e;
     a.in = in; a.in2 = in2; a.wp = packed_w; a.out = out;
     a.scale = scale; a.shift = shift; a.res = residual; a.relu = relu;
     return dispatch_mode<0>(a, mode, precision, cin, cout, src, az_stream(stream));
+}
+
+// partial-buffer rows of a depth-rolling kernel, which counts them from the launch geometry
+template <class F>
+static long long roll_stats_tiles(int mode, int B, int Di, int Hi, int Wi, F tiles_of) {
+    ConvArgs a{};
+    if (int e = conv_common(a, mode, B, Di, Hi, Wi)) return e;
+    return tiles_of(a);
 }
 
 // rows of the partial buffers az_conv3d_fwd_stats fills when called with the same arguments (the depth-rolling
@@ -727,9 +650,7 @@ extern "C" int az_conv3d_fwd(float *out, const float *in, const float *in2,
 extern "C" long long az_conv3d_stats_tiles(int mode, int precision, int B, int cin, int cout, int Di, int Hi, int Wi) {
     if (precision == 2) {
         if (mode != 0 || cout != 32) return AZ_EUNSUPPORTED;
-        ConvArgs a{};
-        if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, 0)) return e;
-        return az_conv3d_roll_stats_tiles(a);
+        return roll_stats_tiles(mode, B, Di, Hi, Wi, [](const ConvArgs &a) { return az_conv3d_roll_stats_tiles(a); });
     }
     return az_conv3d_num_tiles(mode, B, Di, Hi, Wi);
 }
@@ -742,7 +663,7 @@ extern "C" int az_conv3d_fwd_stats(float *out, float *partials, float *counts, c
     AZ_REQUIRE_PTR(partials); AZ_REQUIRE_PTR(counts);
     if (src == 1) AZ_REQUIRE_PTR(in2);
     ConvArgs a{};
-    if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, src)) return e;
+    if (int e = conv_common(a, mode, B, Di, Hi, Wi)) return e;
     a.in = in; a.in2 = in2; a.wp = packed_w; a.out = out; a.part = partials; a.cnt = counts;
     a.ntiles = az_conv3d_stats_tiles(mode, precision, B, cin, cout, Di, Hi, Wi);
     if (a.ntiles < 0) return (int)a.ntiles;
@@ -781,19 +702,16 @@ extern "C" int az_conv3d_pack_weights_f16(float *packed, const float *w, const f
         return az_conv3d_pack_r16_f16(packed, w, w_amax, cin, cout, stride_out, stride_in, flip, az_stream(stream),
                                       f16_on_roll64(mode, cin, cout) ? 2 : 1);
     const int total = 27 * cin * cout * 2;
-    hipLaunchKernelGGL(conv3d_pack_f16_kernel, dim3((total + 255) / 256), dim3(256), 0, az_stream(stream),
+    hipLaunchKernelGGL(conv3d_pack_parts_kernel<true>, dim3((total + 255) / 256), dim3(256), 0, az_stream(stream),
                        reinterpret_cast<unsigned short *>(packed), w, w_amax, cin, cout, stride_out, stride_in, flip, total);
     return az_launch_status();
 }
 
 static int conv_f16_dispatch(ConvArgs &a, int mode, int cin, int cout, int epi, hipStream_t s) {
     if (f16_on_roll(mode, cin, cout)) return az_conv3d_roll_launch_f16(a, cin, epi, s, cout);
-    if (f16_on_t2roll(mode, cin, cout)) {
-        const int rc = az_conv3d_t2roll_launch(a, epi, s);
-        if (rc != AZ_EUNSUPPORTED) return rc;
-        return AZ_EUNSUPPORTED;  // (the weights are packed for that kernel: the caller takes the bf16x6 route)
-    }
-    if (f16_on_s2roll(mode, cin, cout)) return az_conv3d_s2roll_launch(a, epi, s);  // (AZ_EUNSUPPORTED: as above)
+    // (AZ_EUNSUPPORTED from these two: the weights are packed for that kernel, so the caller takes the bf16x6 route)
+    if (f16_on_t2roll(mode, cin, cout)) return az_conv3d_t2roll_launch(a, epi, s);
+    if (f16_on_s2roll(mode, cin, cout)) return az_conv3d_s2roll_launch(a, epi, s);
     return epi ? dispatch_mode<1>(a, mode, 3, cin, cout, 0, s) : dispatch_mode<0>(a, mode, 3, cin, cout, 0, s);
 }
 
@@ -815,7 +733,7 @@ extern "C" int az_conv3d_fwd_f16(float *out, const float *in, const float *packe
                                  void *stream) {
     AZ_REQUIRE_PTR(out); AZ_REQUIRE_PTR(in); AZ_REQUIRE_PTR(packed_w); AZ_REQUIRE_PTR(in_amax); AZ_REQUIRE_PTR(w_amax);
     ConvArgs a{};
-    if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, 0)) return e;
+    if (int e = conv_common(a, mode, B, Di, Hi, Wi)) return e;
     if (in_split && !az_conv3d_fwd_f16_split_ok(mode, B, cin, cout, Di, Hi, Wi)) return AZ_EUNSUPPORTED;
     a.in = in; a.wp = packed_w; a.out = out; a.scale = scale; a.shift = shift; a.res = residual; a.relu = relu;
     a.in_amax = in_amax; a.w_amax = w_amax; a.in_split = in_split ? 1 : 0;
@@ -824,22 +742,13 @@ extern "C" int az_conv3d_fwd_f16(float *out, const float *in, const float *packe
 
 extern "C" long long az_conv3d_stats_tiles_f16(int mode, int B, int cin, int cout, int Di, int Hi, int Wi) {
     if (mode < 0 || mode > 2) return AZ_EINVAL;
-    if (f16_on_roll64(mode, cin, cout)) {
-        ConvArgs a{};
-        if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, 0)) return e;
-        return az_conv3d_roll_stats_tiles(a, 64);
-    }
+    if (f16_on_roll64(mode, cin, cout))
+        return roll_stats_tiles(mode, B, Di, Hi, Wi, [](const ConvArgs &a) { return az_conv3d_roll_stats_tiles(a, 64); });
     if (f16_on_roll(mode, cin, cout)) return az_conv3d_stats_tiles(mode, 2, B, cin, cout, Di, Hi, Wi);
-    if (f16_on_t2roll(mode, cin, cout)) {
-        ConvArgs a{};
-        if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, 0)) return e;
-        return az_conv3d_t2roll_stats_tiles(a);
-    }
-    if (f16_on_s2roll(mode, cin, cout)) {
-        ConvArgs a{};
-        if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, 0)) return e;
-        return az_conv3d_s2roll_stats_tiles(a);
-    }
+    if (f16_on_t2roll(mode, cin, cout))
+        return roll_stats_tiles(mode, B, Di, Hi, Wi, [](const ConvArgs &a) { return az_conv3d_t2roll_stats_tiles(a); });
+    if (f16_on_s2roll(mode, cin, cout))
+        return roll_stats_tiles(mode, B, Di, Hi, Wi, [](const ConvArgs &a) { return az_conv3d_s2roll_stats_tiles(a); });
     return az_conv3d_num_tiles(mode, B, Di, Hi, Wi);
 }
 
@@ -849,7 +758,7 @@ extern "C" int az_conv3d_fwd_stats_f16(float *out, float *partials, float *count
     AZ_REQUIRE_PTR(out); AZ_REQUIRE_PTR(in); AZ_REQUIRE_PTR(packed_w); AZ_REQUIRE_PTR(in_amax); AZ_REQUIRE_PTR(w_amax);
     AZ_REQUIRE_PTR(partials); AZ_REQUIRE_PTR(counts);
     ConvArgs a{};
-    if (int e = conv_common(a, mode, B, cin, Di, Hi, Wi, 0)) return e;
+    if (int e = conv_common(a, mode, B, Di, Hi, Wi)) return e;
     a.in = in; a.wp = packed_w; a.out = out; a.part = partials; a.cnt = counts; a.in_amax = in_amax; a.w_amax = w_amax;
     a.ntiles = az_conv3d_stats_tiles_f16(mode, B, cin, cout, Di, Hi, Wi);
     if (a.ntiles < 0) return (int)a.ntiles;

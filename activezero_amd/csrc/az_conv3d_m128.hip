@@ -17,6 +17,7 @@
 // Arithmetic is identical to az_conv3d.hip PREC 1 (six bf16 MFMAs per K16 block, smallest
 // terms first, fp32 accumulate) except for the order in which K16 blocks are accumulated.
 #include "az_conv3d_args.h"
+#include "az_gather_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -26,7 +27,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define M1_SY 10
 #define M1_SX 18
 #define M1_SXP 20  // LDS row pitch in voxels (== 4 mod 8, see above)
-#define M1_VS 24   // dwords per slab voxel
+#define M1_VS AZ_S24_VS  // dwords per slab voxel
 #define M1_BAND 2  // 8-row tile rows per band of the block -> tile order (16 rows, as CV_BAND)
 
 // Diagnostic build only (-DCV_STAMP): whole-wave shader cycles and 100 MHz real-time ticks, summed
@@ -50,30 +51,10 @@ conv3d_m128_kernel(const ConvArgs a) {
     __shared__ __attribute__((aligned(16))) float slab[M1_SY * M1_SXP * M1_VS];
     const int lane = threadIdx.x;
 
-    // ---- block -> tile (XCD chunking + banded order, as az_conv3d.hip) ----------------------
-    int lin = blockIdx.x;
-    if (a.map_mode >= 1) {
-        const int nblk = gridDim.x, xcd = blockIdx.x & 7, q8 = nblk >> 3, r8 = nblk & 7;
-        lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    }
-    const int tyb = (a.tiles_y + 1) >> 1;  // 8-row tile rows (a.tiles_y counts 4-row tiles)
-    const int tix = lin % a.tiles_x; lin /= a.tiles_x;
-    int tiy, td, b;
-    if (a.map_mode >= 2) {
-        const int per_b = a.Dt * tyb;
-        b = lin / per_b;
-        int l = lin - b * per_b;
-        const int full = (tyb / M1_BAND) * M1_BAND * a.Dt;
-        int band, rows;
-        if (l < full) { band = l / (M1_BAND * a.Dt); l -= band * M1_BAND * a.Dt; rows = M1_BAND; }
-        else { band = tyb / M1_BAND; l -= full; rows = tyb - band * M1_BAND; }
-        td = l / rows;
-        tiy = band * M1_BAND + (l - td * rows);
-    } else {
-        tiy = lin % tyb; lin /= tyb;
-        td = lin % a.Dt;
-        b = lin / a.Dt;
-    }
+    // ---- block -> tile (XCD chunking + banded order, as az_conv3d.hip); a.tiles_y counts 4-row tiles ----
+    int tix, tiy, td, b;
+    az_conv_tile_decode(a.map_mode >= 1 ? az_xcd_map(blockIdx.x, gridDim.x) : blockIdx.x, a.map_mode, M1_BAND, a.tiles_x,
+                        (a.tiles_y + 1) >> 1, a.Dt, tix, tiy, td, b);
     const int ty0 = tiy * M1_TY, tx0 = tix * M1_TX;
     const int ih0 = ty0 - 1, iw0 = tx0 - 1;
 
@@ -130,15 +111,7 @@ conv3d_m128_kernel(const ConvArgs a) {
 #pragma unroll
         for (int it = 0; it < NLD; ++it) {
             if (!((okbits >> it) & 1u)) pre[it] = make_float4(0.f, 0.f, 0.f, 0.f);  // zero padding
-            if (lane + 64 * it < NQ) {
-                uint2 hi, mid, lo;
-                az_split3_bf16x4(pre[it], hi, mid, lo);
-                unsigned *dst = reinterpret_cast<unsigned *>(slab) + (sy * M1_SXP + sx) * M1_VS +
-                                (((j >> 1) ^ (sy & 1)) * 4) + (j & 1) * 2;
-                *reinterpret_cast<uint2 *>(dst) = hi;
-                *reinterpret_cast<uint2 *>(dst + 8) = mid;
-                *reinterpret_cast<uint2 *>(dst + 16) = lo;
-            }
+            if (lane + 64 * it < NQ) az_s24_commit<0>(reinterpret_cast<unsigned *>(slab), sy, sx, j, M1_SXP, pre[it], 1.f);
             sx += 16;
             if (sx >= M1_SX) { sx -= M1_SX; ++sy; }
         }
@@ -156,12 +129,10 @@ conv3d_m128_kernel(const ConvArgs a) {
     // A fragments: two per-lane base addresses (row parity decides the half swap), everything
     // else is a compile-time offset of the ds_read
     const float *abase[2];
-    abase[0] = &slab[(rty * M1_SXP + rtx) * M1_VS + ((half ^ (rty & 1)) * 4)];
-    abase[1] = &slab[(rty * M1_SXP + rtx) * M1_VS + ((half ^ ((rty + 1) & 1)) * 4)];
+    abase[0] = &slab[az_s24_read_base(rty, rtx, half, 0, M1_SXP)];
+    abase[1] = &slab[az_s24_read_base(rty, rtx, half, 1, M1_SXP)];
     auto load_a = [&](float4 (&aq)[3], int m, int eh, int ew) {
-        const float *ap = abase[eh & 1] + ((4 * (m >> 1) + eh) * M1_SXP + 8 * (m & 1) + ew) * M1_VS;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) aq[p] = *reinterpret_cast<const float4 *>(ap + 8 * p);
+        az_s24_load<3>(aq, abase[eh & 1] + ((4 * (m >> 1) + eh) * M1_SXP + 8 * (m & 1) + ew) * M1_VS);
     };
     // fp32 product on the bf16 pipe, one accumulator rounding per K16 block (az_common.h az_mfma6_now:
     //  one temporary, added at once: the adds wait for the block's last MFMA and the SIMD's other wave
@@ -228,13 +199,13 @@ conv3d_m128_kernel(const ConvArgs a) {
 
     // ---- epilogue -----------------------------------------------------------------------------
     // C/D map of the 32x32 MFMA: column (out channel) = lane & 31, row (voxel of the 4x8 tile) =
-    // (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); M-tile m covers rows 4(m>>1).., cols 8(m&1)..
+    // az_mfma32_c_row_h; M-tile m covers rows 4(m>>1).., cols 8(m&1)..
     const size_t plane_el = (((size_t)b * a.Do + td) * a.Ho) * a.Wo * 32;
     float *outp = a.out + plane_el;
     const float *resp = a.res ? a.res + plane_el : nullptr;
     const bool full = (ty0 + M1_TY - 1 < a.Ho) && (tx0 + M1_TX - 1 < a.Wo);
     auto voxel = [&](int m, int r, unsigned &off) -> bool {
-        const int vrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int vrow = az_mfma32_c_row_h(half, r);
         const int oh = ty0 + 4 * (m >> 1) + (vrow >> 3), ow = tx0 + 8 * (m & 1) + (vrow & 7);
         off = (unsigned)(oh * a.Wo + ow) * 32 + row;
         return full || ((oh < a.Ho) && (ow < a.Wo));
@@ -246,11 +217,7 @@ conv3d_m128_kernel(const ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 unsigned off;
-                if (!voxel(m, r, off)) continue;
-                float y = acc[m][r] * sc + sf;
-                if (resp) y += resp[off];
-                if (a.relu) y = fmaxf(y, 0.f);
-                outp[off] = y;
+                if (voxel(m, r, off)) az_store_affine(outp, resp, off, acc[m][r], sc, sf, a.relu);
             }
     } else {
         // BatchNorm partials keep az_conv3d.hip's granularity: one (sum, centred M2, count) entry
@@ -272,26 +239,10 @@ conv3d_m128_kernel(const ConvArgs a) {
                         outp[off] = acc[my * 2 + mx][r];
                     }
                 }
-            const int ntot = nvalid + __shfl_xor(nvalid, 32);
-            float sm = 0.f, m2 = 0.f;
-#pragma unroll
-            for (int mx = 0; mx < 2; ++mx)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sm += ((okmask >> (mx * 16 + r)) & 1u) ? acc[my * 2 + mx][r] : 0.f;
-            sm += __shfl_xor(sm, 32);
-            const float mean = sm / (float)max(ntot, 1);
-#pragma unroll
-            for (int mx = 0; mx < 2; ++mx)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float dlt = acc[my * 2 + mx][r] - mean;
-                    m2 += ((okmask >> (mx * 16 + r)) & 1u) ? dlt * dlt : 0.f;
-                }
-            m2 += __shfl_xor(m2, 32);
-            const int tile_id = ((b * a.Dt + td) * a.tiles_y + tiy4) * a.tiles_x + tix;
-            if (half == 0)
-                *reinterpret_cast<float2 *>(&a.part[((size_t)row * a.ntiles + tile_id) * 2]) = make_float2(sm, m2);
-            if (lane == 0) a.cnt[tile_id] = (float)ntot;
+            float sm, m2;
+            const int ntot = az_tile_moments<2, false>(okmask, nvalid, [&](int mx, int r) { return acc[my * 2 + mx][r]; }, sm, m2);
+            az_tile_moments_store(a.part, a.cnt, a.ntiles, row, ((b * a.Dt + td) * a.tiles_y + tiy4) * a.tiles_x + tix, half,
+                                  sm, m2, ntot);
         }
     }
 #ifdef CV_STAMP

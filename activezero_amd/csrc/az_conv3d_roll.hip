@@ -108,13 +108,7 @@ conv3d_roll_kernel(const ConvArgs a) {
     // f16x3: power-of-two operand scales from the tensors' largest magnitudes (device scalars)
     float in_scale = 1.f;
     int out_exp = 0;
-    if (AR) {
-        // (wave-uniform: kept in scalar registers)
-        const int ki = az_f16_scale_exp(az_amax_read(a.in_amax));
-        const int kw = az_f16_scale_exp(az_amax_read(a.w_amax));
-        in_scale = az_pow2(ki);
-        out_exp = -(ki + kw);
-    }
+    if (AR) az_f16_scales(a.in_amax, a.w_amax, in_scale, out_exp);  // (wave-uniform: kept in scalar registers)
 
     f32x4 acc[3][4];  // [slot: kd = 0 -> output p+1, 1 -> p, 2 -> p-1][4x4-voxel tile of this wave's 4x16 half patch]
 #pragma unroll

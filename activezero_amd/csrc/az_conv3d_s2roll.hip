@@ -92,10 +92,9 @@ conv3d_s2roll_kernel(const ConvArgs a) {
     const auto rs_cnt = __builtin_amdgcn_make_buffer_rsrc(EPI == 1 ? a.cnt : a.out, 0, EPI == 1 ? (unsigned)(a.ntiles * 4) : 0u, 0x00020000);
     const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.wp), 0, 27u * S2R_TAPB, 0x00020000);
 
-    const int ki = az_f16_scale_exp(az_amax_read(a.in_amax));
-    const int kw_ = az_f16_scale_exp(az_amax_read(a.w_amax));
-    const float in_scale = az_pow2(ki);
-    const int out_exp = -(ki + kw_);
+    float in_scale;
+    int out_exp;
+    az_f16_scales(a.in_amax, a.w_amax, in_scale, out_exp);
 
     // accumulators: [set][tile]; set 0: output plane t (the one being completed), set 1: plane t + 1 (begun by kd = 0)
     f32x4 acc[2][S2R_NTILE];

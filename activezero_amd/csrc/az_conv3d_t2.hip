@@ -20,12 +20,12 @@
 #include <type_traits>
 
 #include "az_conv3d_args.h"
-#include "az_roll_common.h"
+#include "az_gather_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));  // (= az_f32x16h)
 
 #define T2_PITCH 20  // LDS row pitch in voxels (== 4 mod 8)
-#define T2_VS 24     // dwords per slab voxel
+#define T2_VS AZ_S24_VS  // dwords per slab voxel
 #define T2_SY 5
 #define T2_SX 17
 #define T2_BAND 4
@@ -65,11 +65,7 @@ __device__ __forceinline__ void t2_wave(const ConvArgs &a, float *slab, int b, i
     constexpr int NCH = CIN / 16, NCH32 = CIN / 32;
     constexpr int NP = AR ? 2 : 3, NF = AR ? 4 : 6;
     float in_scale = 1.f, osc = 1.f;
-    if (AR) {
-        const int ki = az_f16_scale_exp(az_amax_read(a.in_amax)), kw_ = az_f16_scale_exp(az_amax_read(a.w_amax));
-        in_scale = az_pow2(ki);
-        osc = ldexpf(1.f, -(ki + kw_));
-    }
+    if (AR) az_f16_scales(a.in_amax, a.w_amax, in_scale, osc);
     constexpr int SLAB = T2_SY * T2_PITCH * T2_VS;
     constexpr int NQ = T2_SY * T2_SX * 4, NLD = (NQ + 255) / 256;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -112,19 +108,7 @@ __device__ __forceinline__ void t2_wave(const ConvArgs &a, float *slab, int b, i
             const int q = tid + 256 * it, vox = q >> 2, j = q & 3;
             const int sy = vox / T2_SX, sx = vox - sy * T2_SX;
             if (!((okbits >> it) & 1u)) pre[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q < NQ) {
-                uint2 hi, mid, lo;
-                if (AR) {
-                    az_split2_f16x4(make_float4(pre[it].x * in_scale, pre[it].y * in_scale, pre[it].z * in_scale, pre[it].w * in_scale), hi, mid);
-                    lo = mid;
-                } else {
-                    az_split3_bf16x4(pre[it], hi, mid, lo);
-                }
-                unsigned *dst = sb + (sy * T2_PITCH + sx) * T2_VS + (((j >> 1) ^ (sy & 1)) * 4) + (j & 1) * 2;
-                *reinterpret_cast<uint2 *>(dst) = hi;
-                *reinterpret_cast<uint2 *>(dst + 8) = mid;
-                if (!AR) *reinterpret_cast<uint2 *>(dst + 16) = lo;
-            }
+            if (q < NQ) az_s24_commit<AR>(sb, sy, sx, j, T2_PITCH, pre[it], in_scale);
         }
     };
     // packed weights [tap][cin/32][n = 0][part*2 + kb][lane] float4 (az_conv3d.hip), kb = odd 16-channel chunk
@@ -134,12 +118,10 @@ __device__ __forceinline__ void t2_wave(const ConvArgs &a, float *slab, int b, i
         for (int k = 0; k < NP; ++k) bq[k] = p[k * 2 * 64];
     };
     const float *abase[2];
-    abase[0] = &slab[(rty * T2_PITCH + rtx) * T2_VS + ((half ^ (rty & 1)) * 4)];
-    abase[1] = &slab[(rty * T2_PITCH + rtx) * T2_VS + ((half ^ ((rty + 1) & 1)) * 4)];
+    abase[0] = &slab[az_s24_read_base(rty, rtx, half, 0, T2_PITCH)];
+    abase[1] = &slab[az_s24_read_base(rty, rtx, half, 1, T2_PITCH)];
     auto load_a = [&](float4 (&aq)[3], int buf, int m, int oh, int ow) {
-        const float *ap = abase[oh & 1] + buf * SLAB + (oh * T2_PITCH + 8 * m + ow) * T2_VS;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) aq[p] = *reinterpret_cast<const float4 *>(ap + 8 * p);
+        az_s24_load<NP>(aq, abase[oh & 1] + buf * SLAB + (oh * T2_PITCH + 8 * m + ow) * T2_VS);
     };
 
     issue(0);
@@ -215,15 +197,12 @@ __device__ __forceinline__ void t2_wave(const ConvArgs &a, float *slab, int b, i
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int vrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int vrow = az_mfma32_c_row_h(half, r);
                 const int th = ty0 + (vrow >> 3), tw = tx0 + 8 * m + (vrow & 7);
                 if (th >= a.Hi || tw >= a.Wi) continue;
                 const unsigned off = (unsigned)((2 * th + ph) * a.Wo + 2 * tw + pw) * 32 + row;
                 if (EPI == 0) {
-                    float y = acc[q][m][r] * sc + sf;
-                    if (resp) y += resp[off];
-                    if (a.relu) y = fmaxf(y, 0.f);
-                    outp[off] = y;
+                    az_store_affine(outp, resp, off, acc[q][m][r], sc, sf, a.relu);
                 } else {
                     outp[off] = acc[q][m][r];
                     okmask |= 1u << (m * 16 + r);
@@ -231,26 +210,10 @@ __device__ __forceinline__ void t2_wave(const ConvArgs &a, float *slab, int b, i
                 }
             }
         if (EPI == 1) {
-            const int ntot = nvalid + __shfl_xor(nvalid, 32);
-            float sm = 0.f, m2 = 0.f;
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sm += ((okmask >> (m * 16 + r)) & 1u) ? acc[q][m][r] : 0.f;
-            sm += __shfl_xor(sm, 32);
-            const float mean = sm / (float)max(ntot, 1);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float dlt = acc[q][m][r] - mean;
-                    m2 += ((okmask >> (m * 16 + r)) & 1u) ? dlt * dlt : 0.f;
-                }
-            m2 += __shfl_xor(m2, 32);
-            const int tile_id = ((((b * a.Dt + td) * a.tiles_y + tiy) * a.tiles_x + tix) << 3) + p;
-            if (half == 0)
-                *reinterpret_cast<float2 *>(&a.part[((size_t)row * a.ntiles + tile_id) * 2]) = make_float2(sm, m2);
-            if (lane == 0) a.cnt[tile_id] = (float)ntot;
+            float sm, m2;
+            const int ntot = az_tile_moments<2, false>(okmask, nvalid, [&](int m, int r) { return acc[q][m][r]; }, sm, m2);
+            az_tile_moments_store(a.part, a.cnt, a.ntiles, row, ((((b * a.Dt + td) * a.tiles_y + tiy) * a.tiles_x + tix) << 3) + p,
+                                  half, sm, m2, ntot);
         }
     }
 }
@@ -259,28 +222,9 @@ template <int CIN, int EPI, int AR>
 __global__ void __launch_bounds__(256, 2)
 conv3d_t2_kernel(const ConvArgs a) {
     __shared__ __attribute__((aligned(16))) float slab[2 * T2_SY * T2_PITCH * T2_VS];
-    int lin = blockIdx.x;
-    if (a.map_mode >= 1) {
-        const int nblk = gridDim.x, xcd = blockIdx.x & 7, q8 = nblk >> 3, r8 = nblk & 7;
-        lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    }
-    const int tix = lin % a.tiles_x; lin /= a.tiles_x;
-    int tiy, td, b;
-    if (a.map_mode >= 2) {  // banded: x fastest, then T2_BAND tile rows, then the depth index
-        const int per_b = a.Dt * a.tiles_y;
-        b = lin / per_b;
-        int l = lin - b * per_b;
-        const int full = (a.tiles_y / T2_BAND) * T2_BAND * a.Dt;
-        int band, rows;
-        if (l < full) { band = l / (T2_BAND * a.Dt); l -= band * T2_BAND * a.Dt; rows = T2_BAND; }
-        else { band = a.tiles_y / T2_BAND; l -= full; rows = a.tiles_y - band * T2_BAND; }
-        td = l / rows;
-        tiy = band * T2_BAND + (l - td * rows);
-    } else {
-        tiy = lin % a.tiles_y; lin /= a.tiles_y;
-        td = lin % a.Dt;
-        b = lin / a.Dt;
-    }
+    int tix, tiy, td, b;
+    az_conv_tile_decode(a.map_mode >= 1 ? az_xcd_map(blockIdx.x, gridDim.x) : blockIdx.x, a.map_mode, T2_BAND, a.tiles_x,
+                        a.tiles_y, a.Dt, tix, tiy, td, b);
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wv == 0) t2_wave<CIN, EPI, 0, AR>(a, slab, b, td, tiy, tix);
     else if (wv == 1) t2_wave<CIN, EPI, 1, AR>(a, slab, b, td, tiy, tix);
@@ -288,16 +232,19 @@ conv3d_t2_kernel(const ConvArgs a) {
     else t2_wave<CIN, EPI, 3, AR>(a, slab, b, td, tiy, tix);
 }
 
+template <int CIN, int EPI>
+static int launch_t2(const ConvArgs &a, bool f16, unsigned blocks, hipStream_t s) {
+    if (f16) hipLaunchKernelGGL((conv3d_t2_kernel<CIN, EPI, 1>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((conv3d_t2_kernel<CIN, EPI, 0>), dim3(blocks), dim3(256), 0, s, a);
+    return az_launch_status();
+}
+
 int az_conv3d_t2_launch(const ConvArgs &a, int cin, int epi, hipStream_t s) {
     const long long blocks = (long long)a.B * a.Dt * a.tiles_y * a.tiles_x;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return AZ_EUNSUPPORTED;
     if ((long long)a.Ho * a.Wo * 32 > 0x7fffffffLL) return AZ_EUNSUPPORTED;
     const bool f16 = a.in_amax != nullptr && a.w_amax != nullptr;
-#define T2_LAUNCH(CIN, EPI) do { if (f16) hipLaunchKernelGGL((conv3d_t2_kernel<CIN, EPI, 1>), dim3((unsigned)blocks), dim3(256), 0, s, a); \
-                                 else hipLaunchKernelGGL((conv3d_t2_kernel<CIN, EPI, 0>), dim3((unsigned)blocks), dim3(256), 0, s, a); } while (0)
-    if (cin == 64) { if (epi) T2_LAUNCH(64, 1); else T2_LAUNCH(64, 0); }
-    else if (cin == 32) { if (epi) T2_LAUNCH(32, 1); else T2_LAUNCH(32, 0); }
-    else return AZ_EUNSUPPORTED;
-#undef T2_LAUNCH
-    return az_launch_status();
+    if (cin == 64) return epi ? launch_t2<64, 1>(a, f16, (unsigned)blocks, s) : launch_t2<64, 0>(a, f16, (unsigned)blocks, s);
+    if (cin == 32) return epi ? launch_t2<32, 1>(a, f16, (unsigned)blocks, s) : launch_t2<32, 0>(a, f16, (unsigned)blocks, s);
+    return AZ_EUNSUPPORTED;
 }

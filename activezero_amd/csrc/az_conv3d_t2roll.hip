@@ -99,10 +99,9 @@ conv3d_t2roll_kernel(const ConvArgs a) {
     const auto rs_cnt = __builtin_amdgcn_make_buffer_rsrc(EPI == 1 ? a.cnt : a.out, 0, EPI == 1 ? (unsigned)(a.ntiles * 4) : 0u, 0x00020000);
     const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.wp), 0, 27u * T2R_TAPF4 * 16u, 0x00020000);
 
-    const int ki = az_f16_scale_exp(az_amax_read(a.in_amax));
-    const int kw_ = az_f16_scale_exp(az_amax_read(a.w_amax));
-    const float in_scale = az_pow2(ki);
-    const int out_exp = -(ki + kw_);
+    float in_scale;
+    int out_exp;
+    az_f16_scales(a.in_amax, a.w_amax, in_scale, out_exp);
 
     // accumulators: [set][phase ph * 2 + pw][tile]; set 0: carried (fine plane 2z - 1), 1: fine plane 2z, 2: next (2z + 1)
     f32x4 acc[3][4][2];

@@ -215,7 +215,7 @@ conv3d_wgrad_x6_kernel(const WgArgs a) {
     constexpr int WCH = X6_WCH;
     constexpr int NP = AR ? 2 : 3;
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
+    if (AR) az_f16_scales(a.coarse_amax, a.fine_amax, c_scale, o_scale, &f_scale);
     constexpr int FW = S * (WCH - 1) + 3;  // fine positions per staged row
     constexpr int MT = CM / 32, NT = CN / 32, NCOMBO = 3 * MT * NT;
     constexpr int NEW = S;

@@ -81,7 +81,7 @@ conv3d_wgrad_r16_kernel(const Wg16Args a) {
 #pragma unroll
     for (int t = 0; t < 27; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     float c_scale = 1.f, f_scale = 1.f, o_scale = 1.f;
-    if (AR) az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
+    if (AR) az_f16_scales(a.coarse_amax, a.fine_amax, c_scale, o_scale, &f_scale);
 
     // transposing-read geometry and the row-half swap against bank conflicts: az_w16_lanes (az_launch_math.h), written out
     // (called as a function it moves this kernel's registers: <1, .> 244 -> 243, <0, 0> 11 -> 7 spilled)

@@ -89,7 +89,7 @@ conv3d_wgrad_s2r16_kernel(const Wg16s2Args a) {
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) acc[t][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
     float c_scale, f_scale, o_scale;
-    az_wgrad_scales(a.coarse_amax, a.fine_amax, c_scale, f_scale, o_scale);
+    az_f16_scales(a.coarse_amax, a.fine_amax, c_scale, o_scale, &f_scale);
 
     // transposing-read geometry (ds_read_b64_tr_b16 on a [k][32 ch] image, az_conv3d_wgrad16.hip): a 16-lane group = one K
     // octet = one coarse row of the step; lane 4q + p supplies the address of k-row q (position q, then q + 4), channels

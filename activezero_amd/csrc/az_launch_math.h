@@ -16,6 +16,46 @@ AZ_HD int az_xcd_map(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
+// Block -> tile map of the gather kernels (az_conv3d.hip, az_conv3d_m128.hip, az_conv3d_t2.hip): position `lin` of the linear
+// tile order (map_mode 0: the block id; >= 1: az_xcd_map of it, so that an XCD walks a contiguous chunk) -> patch column tix,
+// tile row tiy < rows_y, depth index td < Dt, batch entry b.  map_mode < 2: the plain mixed radix, x fastest, then rows,
+// depth, batch.  map_mode >= 2, banded: x fastest, then the band_rows tile rows of a band, then the depth index, then the
+// band (the last one may have fewer rows) -- the three output planes that read one input plane, and the row halos inside a
+// band, are processed back to back and hit in L2.  A bijection of [0, B * Dt * rows_y * tiles_x) onto the tiles either way.
+AZ_HD void az_conv_tile_decode(int lin, int map_mode, int band_rows, int tiles_x, int rows_y, int Dt, int &tix, int &tiy,
+                               int &td, int &b) {
+    tix = lin % tiles_x; lin /= tiles_x;
+    if (map_mode >= 2) {
+        const int per_b = Dt * rows_y;
+        b = lin / per_b;
+        int l = lin - b * per_b;
+        const int full = (rows_y / band_rows) * band_rows * Dt;  // blocks in the complete bands
+        int band, rows;
+        if (l < full) { band = l / (band_rows * Dt); l -= band * band_rows * Dt; rows = band_rows; }
+        else { band = rows_y / band_rows; l -= full; rows = rows_y - band * band_rows; }
+        td = l / rows;
+        tiy = band * band_rows + (l - td * rows);
+    } else {
+        tiy = lin % rows_y; lin /= rows_y;
+        td = lin % Dt;
+        b = lin / Dt;
+    }
+}
+
+// The 24-dword slab image of az_conv3d_m128.hip, az_conv3d_t2.hip and az_conv2d.hip: a voxel is up to three 8-dword parts
+// (16 channels of 16-bit values each) and a row is `pitch` voxels (== 4 mod 8); the two 16-byte halves of a part are swapped
+// on odd rows, which makes the ds_read_b128 of an A fragment conflict-free without padding (az_conv3d_m128.hip).
+// Writing: dword offset of the 8-byte piece j (channels 4j .. 4j + 3 of the chunk) of part 0 of voxel (sy, sx); part p: + 8p.
+#define AZ_S24_VS 24
+AZ_HD int az_s24_write_off(int sy, int sx, int j, int pitch) {
+    return (sy * pitch + sx) * AZ_S24_VS + ((j >> 1) ^ (sy & 1)) * 4 + (j & 1) * 2;
+}
+// Reading: the 16 bytes = channels 8 half .. 8 half + 7 of part 0 that fragment lane (voxel (rty, rtx) of its 4x8 tile, K
+// half `half`) takes from the voxel (dy, dx) further on, dy of the given parity; the read adds (dy * pitch + dx) * AZ_S24_VS.
+AZ_HD int az_s24_read_base(int rty, int rtx, int half, int parity, int pitch) {
+    return (rty * pitch + rtx) * AZ_S24_VS + (half ^ ((rty + parity) & 1)) * 4;
+}
+
 // az_conv3d_roll.hip: depth segments of a launch -- one round of workgroups over the chip's 512 slots (256 CUs x 2) if the
 // patches allow it, otherwise the split that minimises rounds x (planes walked per workgroup).  patches = B * 8-row patch
 // rows * patch columns; forced > 0: that segment length (AZ_ROLL_SEGLEN).  Postconditions: nseg * seg_len >= Do,
@@ -151,9 +191,12 @@ inline int az_wgrad16_workgroups(long long ncols, int slots, int ntiles, int cap
     return best;
 }
 
-// C layout of the two MFMA shapes the weight-gradient kernels flush (az_wgrad_common.h): register `reg` of lane `lane` holds
-// element (row, col) of the tile -- 32x32: 16 registers, 16x16: 4 registers.
-AZ_HD int az_mfma32_c_row(int lane, int reg) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+// C layout of the two MFMA shapes the weight-gradient kernels flush (az_wgrad_common.h) and the gather kernels store
+// (az_gather_common.h): register `reg` of lane `lane` holds element (row, col) of the tile -- 32x32: 16 registers, 16x16: 4
+// registers.  (_h: by the lane's half-wave lane >> 5, for kernels that keep it -- hipcc does not merge a second lane >> 5
+// with theirs, and az_conv3d.hip then spills in 11 instantiations.)
+AZ_HD int az_mfma32_c_row_h(int half, int reg) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+AZ_HD int az_mfma32_c_row(int lane, int reg) { return az_mfma32_c_row_h(lane >> 5, reg); }
 AZ_HD int az_mfma32_c_col(int lane) { return lane & 31; }
 AZ_HD int az_mfma16_c_row(int lane, int reg) { return 4 * (lane >> 4) + reg; }
 AZ_HD int az_mfma16_c_col(int lane) { return lane & 15; }

@@ -72,6 +72,26 @@ __host__ __device__ __forceinline__ int az_f16_scale_exp(float amax) {
     return k < -126 ? -126 : (k > 127 ? 127 : k);
 }
 __host__ __device__ __forceinline__ float az_pow2(int k) { return __builtin_bit_cast(float, (unsigned)(k + 127) << 23); }
+// The wave-uniform power-of-two operand scales of a kernel, from the two tensors' amax arrays (call with all 64 lanes active):
+// in_scale = 2^ki for the operand the kernel scales while staging (w_scale = 2^kw likewise, for kernels that stage both; a
+// packed weight image carries its scale already) and what undoes both on the finished sums -- as the exponent -(ki + kw), or
+// as the factor 2^-(ki + kw).  NULL_OK: an amax array may be null (scale 1).
+template <bool NULL_OK = false>
+__device__ __forceinline__ void az_f16_scales(const float *in_amax, const float *w_amax, float &in_scale, int &out_exp,
+                                              float *w_scale = nullptr) {
+    const int ki = (!NULL_OK || in_amax) ? az_f16_scale_exp(az_amax_read(in_amax)) : 0;
+    const int kw = (!NULL_OK || w_amax) ? az_f16_scale_exp(az_amax_read(w_amax)) : 0;
+    in_scale = az_pow2(ki);
+    if (w_scale) *w_scale = az_pow2(kw);
+    out_exp = -(ki + kw);
+}
+template <bool NULL_OK = false>
+__device__ __forceinline__ void az_f16_scales(const float *in_amax, const float *w_amax, float &in_scale, float &out_scale,
+                                              float *w_scale = nullptr) {
+    int out_exp;
+    az_f16_scales<NULL_OK>(in_amax, w_amax, in_scale, out_exp, w_scale);
+    out_scale = ldexpf(1.f, out_exp);
+}
 
 __device__ __forceinline__ void az_split2_f16_pair(float x0, float x1, unsigned &hi, unsigned &lo) {
     az_f16x2 h, l;

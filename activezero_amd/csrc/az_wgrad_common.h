@@ -1,7 +1,7 @@
 // Shared by the weight-gradient kernels (az_conv3d_wgrad.hip, az_conv3d_wgrad16.hip, az_conv3d_wgrad16s2.hip,
-// az_conv2d_wgrad.hip, az_conv2d_wgrad16.hip): the transposing fragment read, the operand scales and the staging split of
-// the f16x3 arithmetic, the accumulate chains of both MFMA shapes, the tap-major atomic flush, and the launchers the files
-// call across each other.  The lane geometry and C-layout maps are index arithmetic: az_launch_math.h (swept on the CPU).
+// az_conv2d_wgrad.hip, az_conv2d_wgrad16.hip): the transposing fragment read, the staging split of the f16x3 arithmetic
+// (its operand scales: az_f16_scales, az_roll_common.h), the accumulate chains of both MFMA shapes, the tap-major atomic
+// flush, and the launchers the files call across each other.  The lane geometry and C-layout maps are index arithmetic: az_launch_math.h (swept on the CPU).
 #pragma once
 #include <type_traits>
 
@@ -26,17 +26,6 @@ __device__ __forceinline__ s16x8 az_tr16_frag(const void *lo, const void *hi) {
     v[0] = lo4[0]; v[1] = lo4[1]; v[2] = lo4[2]; v[3] = lo4[3];
     v[4] = hi4[0]; v[5] = hi4[1]; v[6] = hi4[2]; v[7] = hi4[3];
     return v;
-}
-
-// wave-uniform power-of-two operand scales of the fp16 arithmetics and the scale that undoes both in the flush;
-// NULL_OK: an amax array may be null (scale 1)
-template <bool NULL_OK = false>
-__device__ __forceinline__ void az_wgrad_scales(const float *coarse_amax, const float *fine_amax, float &c_scale, float &f_scale,
-                                                float &o_scale) {
-    const int kc = (!NULL_OK || coarse_amax) ? az_f16_scale_exp(az_amax_read(coarse_amax)) : 0;
-    const int kf = (!NULL_OK || fine_amax) ? az_f16_scale_exp(az_amax_read(fine_amax)) : 0;
-    c_scale = az_pow2(kc); f_scale = az_pow2(kf);
-    o_scale = ldexpf(1.f, -(kc + kf));
 }
 
 // one MFMA of either shape (by accumulator type) and format; FR: az_bf16x8 or az_f16x8, whichever the kernel keeps

@@ -371,6 +371,74 @@ int main() {
                 if (off >= 0 && off < 32 * AZ_W16_ROWB) seen[off / 8] = 1;
             }
     }
+    // The gather kernels' block -> tile map (az_conv3d.hip, az_conv3d_m128.hip, az_conv3d_t2.hip): with every map mode and
+    // both band heights the blocks of a launch decode into range and hit every (tix, tiy, td, b) exactly once; map mode 0 is
+    // the plain mixed radix of the block id.  Row counts: those of `dims` and every residue of rows_y % band, rows_y < band
+    // and rows_y == 1 among them.
+    {
+        std::vector<std::vector<int>> cases;  // B, Dt, rows_y, tiles_x
+        for (const auto &d : dims) {
+            cases.push_back({d[0], d[1], (d[2] + 3) / 4, (d[3] + 15) / 16});               // 4-row tiles
+            cases.push_back({d[0], d[1], ((d[2] + 3) / 4 + 1) / 2, (d[3] + 15) / 16});     // 8-row tile rows (m128)
+        }
+        for (int rows = 1; rows <= 13; ++rows)
+            for (int Dt = 1; Dt <= 5; Dt += 2) { cases.push_back({1, Dt, rows, 3}); cases.push_back({3, Dt, rows, 1}); }
+        for (const auto &c : cases)
+            for (int map_mode = 0; map_mode <= 2; ++map_mode)
+                for (int band = 2; band <= 4; band += 2) {
+                    const int B = c[0], Dt = c[1], rows_y = c[2], tiles_x = c[3];
+                    const long long nblk = (long long)B * Dt * rows_y * tiles_x;
+                    if (nblk > 400000) continue;
+                    std::vector<char> seen((size_t)nblk, 0);
+                    for (int bid = 0; bid < (int)nblk; ++bid) {
+                        int tix = -1, tiy = -1, td = -1, b = -1;
+                        az_conv_tile_decode(map_mode >= 1 ? az_xcd_map(bid, (int)nblk) : bid, map_mode, band, tiles_x, rows_y, Dt, tix, tiy, td, b);
+                        const bool in = tix >= 0 && tix < tiles_x && tiy >= 0 && tiy < rows_y && td >= 0 && td < Dt && b >= 0 && b < B;
+                        CHECK(in, "tile map %d band %d: block %d of (%d,%d,%d,%d) -> (%d,%d,%d,%d)", map_mode, band, bid, B, Dt, rows_y, tiles_x, b, td, tiy, tix);
+                        if (!in) continue;
+                        const long long id = (((long long)b * Dt + td) * rows_y + tiy) * tiles_x + tix;
+                        CHECK(!seen[(size_t)id], "tile map %d band %d: tile %lld of (%d,%d,%d,%d) twice", map_mode, band, id, B, Dt, rows_y, tiles_x);
+                        seen[(size_t)id] = 1;
+                        if (map_mode == 0) CHECK(id == bid, "tile map 0: block %d -> tile %lld", bid, id);
+                    }
+                }
+    }
+    // The 24-dword slab image (az_conv3d_m128.hip, az_conv3d_t2.hip, az_conv2d.hip): the dword the commit writes for (voxel,
+    // chunk channel, part) is the dword the fragment element that must hold that channel reads -- lane: row = lane & 31 =
+    // voxel (row >> 3, row & 7) of its 4x8 tile, half = lane >> 5; element e of the 16-byte read <-> channel 8 half + e, two
+    // per dword -- and the offsets are distinct and inside the slab.  Slabs: 10 x 18 (m128, conv2d 3x3), 5 x 17 (t2), 12 x 20.
+    {
+        const int slabs[][2] = {{10, 18}, {5, 17}, {12, 20}, {8, 16}};
+        const int pitch = 20;
+        for (const auto &sl : slabs) {
+            const int SY = sl[0], SX = sl[1];
+            std::vector<char> seen((size_t)SY * pitch * AZ_S24_VS, 0);
+            for (int sy = 0; sy < SY; ++sy)
+                for (int sx = 0; sx < SX; ++sx)
+                    for (int part = 0; part < 3; ++part)
+                        for (int j = 0; j < 4; ++j) {  // the 8-byte piece of channels 4j .. 4j + 3
+                            const int off = az_s24_write_off(sy, sx, j, pitch) + 8 * part;
+                            const bool in = off >= 0 && off + 1 < SY * pitch * AZ_S24_VS && off % 2 == 0;
+                            CHECK(in, "slab %dx%d: piece (%d,%d,%d,%d) at %d", SY, SX, sy, sx, part, j, off);
+                            if (!in) continue;
+                            CHECK(!seen[(size_t)off] && !seen[(size_t)off + 1], "slab %dx%d: dword %d written twice", SY, SX, off);
+                            seen[(size_t)off] = seen[(size_t)off + 1] = 1;
+                        }
+            // every lane of a fragment whose tile sits at (dy, dx) inside the slab
+            for (int dy = 0; dy + 4 <= SY; ++dy)
+                for (int dx = 0; dx + 8 <= SX; ++dx)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int part = 0; part < 3; ++part)
+                            for (int e = 0; e < 8; ++e) {
+                                const int row = lane & 31, half = lane >> 5, rty = row >> 3, rtx = row & 7;
+                                const int rd = az_s24_read_base(rty, rtx, half, dy & 1, pitch) + (dy * pitch + dx) * AZ_S24_VS + 8 * part + e / 2;
+                                const int ch = 8 * half + e;
+                                const int wr = az_s24_write_off(rty + dy, rtx + dx, ch >> 2, pitch) + 8 * part + (ch & 3) / 2;
+                                CHECK(rd == wr, "slab %dx%d: lane %d at (%d,%d) part %d element %d reads %d, channel %d is at %d", SY, SX, lane, dy, dx,
+                                      part, e, rd, ch, wr);
+                            }
+        }
+    }
     std::printf("launch math: %d failures\n", fails);
     return fails ? 1 : 0;
 }

@@ -50,6 +50,11 @@ CASES = [
 # selection also runs that file's route-coverage test under the switch.
 S1 = "tests/test_gpu_conv3d_s1.py"
 S1_WGRAD = "stride1_vs_fp64 and wgrad and not fp32 or presplit_operands or accumulate_only or every_route"
+# the bf16x6 forward launches off the rolling kernel, their epilogues (partials; affine + residual + ReLU) element-wise too
+S1_GATHER_X6 = ("(stride1_vs_fp64 or residual_handover) and bf16x6 and not wgrad or every_route"
+                " or (forward_batchnorm_partials or forward_affine_residual_relu_epilogue) and bf16x6")
+# the block -> tile maps (az_conv_tile_decode) at the shapes with more than one tile row, column, plane or batch entry
+S1_TILE_MAP = "stride1_vs_fp64 and fwd and bf16x6 and (2x4x9x16 or 3x2x5x33 or 1x13x25x17) or every_route"
 S1_CASES = [
     ({"AZ_WGRAD_R16_WGS": "3"}, S1, S1_WGRAD),                   # the column walk at every shape with more than 3 columns
     ({"AZ_WGRAD_R16_WGS": "8"}, S1, S1_WGRAD),                   # wgs % 8 == 0: the XCD column map at small shapes
@@ -57,12 +62,14 @@ S1_CASES = [
     ({"AZ_WGRAD_R16_XCD": "0"}, S1, S1_WGRAD + " or full_size"),
     ({"AZ_WGRAD_R16": "0"}, S1, "stride1_vs_fp64 and wgrad and bf16x6 or every_route"),  # one-kd-per-wave bf16x6 kernels
     ({"AZ_WGRAD_R16": "1"}, S1, "stride1_vs_fp64 and wgrad and bf16x6 or every_route"),
-    ({"AZ_CONV_ROLL": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and bf16x6 and not wgrad or every_route"),  # m128
-    ({"AZ_CONV_ROLL": "0", "AZ_CONV_M128": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and bf16x6 and not wgrad or every_route"),
+    ({"AZ_CONV_ROLL": "0"}, S1, S1_GATHER_X6),                     # m128: a dead lower half patch at 1x13x25x17
+    ({"AZ_CONV_ROLL": "0", "AZ_CONV_M128": "0"}, S1, S1_GATHER_X6),  # the gather kernel: a ragged band at 1x13x25x17
     ({"AZ_CONV_ROLL64": "0"}, S1, "(stride1_vs_fp64 or residual_handover) and f16x3 and 64x64 and not wgrad or every_route"),
     ({"AZ_ROLL_SEGLEN": "1"}, S1, "stride1_vs_fp64 and not wgrad and not fp32 or residual_handover or dgrad_presplit or full_size"),
     # multi-plane segments at small shapes (depth 13: 5, 5 and 3 planes; depth 5: one of five): the partials' carried state
     ({"AZ_ROLL_SEGLEN": "5"}, S1, "forward_batchnorm_partials or forward_affine_residual_relu_epilogue or every_route"),
+    ({"AZ_CONV_ROLL": "0", "AZ_CONV_MAP": "0"}, S1, S1_TILE_MAP),   # m128 and the gather kernel on the linear block -> tile map
+    ({"AZ_CONV_ROLL": "0", "AZ_CONV_MAP": "1"}, S1, S1_TILE_MAP),   # ... on the XCD chunks without bands
 ]
 
 
@@ -89,6 +96,7 @@ S2_CASES = [
     ({"AZ_S2ROLL_SEGLEN": "3"}, S2, S2_MODE1_3264),               # multi-plane segments, ragged where Do % 3
     ({"AZ_S2ROLL_SEGLEN": "2"}, S2, S2_MODE1_3264),
     ({"AZ_CONV_MAP": "0"}, S2, f"strided_vs_fp64 and not wgrad and ({S2_MULTI_TILE}) or every_route"),  # linear block -> tile map
+    ({"AZ_CONV_MAP": "1"}, S2, f"strided_vs_fp64 and not wgrad and ({S2_MULTI_TILE}) or every_route"),  # XCD chunks without bands
     ({"AZ_PRESPLIT": "0"}, S2, "presplit or accumulate_only or every_route"),  # the pre-split tests skip, the rest pass
 ]
 
