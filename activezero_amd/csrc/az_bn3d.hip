@@ -194,7 +194,7 @@ bn_apply_kernel(float4 *__restrict__ y, const float4 *__restrict__ x,
             o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
         }
         if (relu) {
-            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+            o.x = az_relu(o.x); o.y = az_relu(o.y); o.z = az_relu(o.z); o.w = az_relu(o.w);  // (a NaN stays: az_common.h)
         }
         bn_st4<NT>(&y[i], o);
         az_amax_acc(am, o);
@@ -481,7 +481,7 @@ add_relu_kernel(float4 *__restrict__ y, const float4 *__restrict__ a,
         const float4 p = a[i], q = b[i];
         float4 o = make_float4(p.x + q.x, p.y + q.y, p.z + q.z, p.w + q.w);
         if (relu) {
-            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+            o.x = az_relu(o.x); o.y = az_relu(o.y); o.z = az_relu(o.z); o.w = az_relu(o.w);  // (a NaN stays: az_common.h)
         }
         y[i] = o;
         az_amax_acc(am, o);

@@ -44,6 +44,14 @@ __device__ __forceinline__ float4 az_ld16_or_zero(const float *base, size_t offs
     return r;
 }
 
+// ---- ReLU and clamps that keep a NaN (include/azhip.h, "Non-finite values").  fmaxf / fminf are IEEE maxNum / minNum
+// (v_max_f32 / v_min_f32): they return the operand that is NOT NaN, so relu(NaN) = 0, and with a floor of -inf NaN becomes
+// -inf.  These are IEEE 754-2019 maximum / minimum (one v_maximum3_f32 / v_minimum3_f32 on gfx950 where fmaxf is two
+// v_max_f32): a NaN on either side is the result, and every other operand pair gives the bits fmaxf / fminf give.
+__device__ __forceinline__ float az_max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float az_min_nan(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float az_relu(float y) { return az_max_nan(y, 0.f); }
+
 // ---- max |x| of a tensor, taken by the kernel that writes it (the operand scale of the f16x3 kernels that read it
 // next; az_absmax.hip is the stand-alone pass).  |x| is compared as a bit pattern: non-negative floats order like
 // unsigned integers; inf / NaN elements are left out (az_finite_abs_bits).

@@ -285,7 +285,7 @@ conv2d_same_kernel(const C2Args a) {
             const unsigned pix = pix0 + dpix;
             float y = acc[m][r] * sc + sf;
             if (resp) y += resp[dpix * (unsigned)a.res_cs];
-            if (a.relu == 1) y = fmaxf(y, 0.f);
+            if (a.relu == 1) y = az_relu(y);
             if constexpr (PARTS == 1) {  // the gate activations exist only in the plain-bf16 (GRU) instantiations
             if (a.relu == 2) y = 1.f / (1.f + __expf(-y));
             else if (a.relu >= 3) {

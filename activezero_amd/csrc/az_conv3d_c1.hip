@@ -100,8 +100,8 @@ c1_fwd_kernel(float *__restrict__ out, const float *__restrict__ in, const float
                 const int q = threadIdx.x + 256 * it;
                 float4 v = pre[it];
                 if (affine && ((okbits >> it) & 1u)) {  // (fmaf + max exactly as az_bn3d_apply rounds)
-                    v.x = fmaxf(fmaf(v.x, isc.x, ish.x), 0.f); v.y = fmaxf(fmaf(v.y, isc.y, ish.y), 0.f);
-                    v.z = fmaxf(fmaf(v.z, isc.z, ish.z), 0.f); v.w = fmaxf(fmaf(v.w, isc.w, ish.w), 0.f);
+                    v.x = az_relu(fmaf(v.x, isc.x, ish.x)); v.y = az_relu(fmaf(v.y, isc.y, ish.y));
+                    v.z = az_relu(fmaf(v.z, isc.z, ish.z)); v.w = az_relu(fmaf(v.w, isc.w, ish.w));
                 }
                 if (q < NQ) *reinterpret_cast<float4 *>(&slab[(q >> 3) * C1_VS + (q & 7) * 4]) = v;
             }
@@ -276,8 +276,8 @@ c1_wgrad_kernel(float *__restrict__ gw, const float *__restrict__ in,
                 if (ih < H && tx0 + lx0 + j < W) {
                     x = *reinterpret_cast<const float4 *>(src + j * 32);
                     if (affine) {  // the operand is relu(in * scale + shift), see c1_fwd_kernel
-                        x.x = fmaxf(fmaf(x.x, isc.x, ish.x), 0.f); x.y = fmaxf(fmaf(x.y, isc.y, ish.y), 0.f);
-                        x.z = fmaxf(fmaf(x.z, isc.z, ish.z), 0.f); x.w = fmaxf(fmaf(x.w, isc.w, ish.w), 0.f);
+                        x.x = az_relu(fmaf(x.x, isc.x, ish.x)); x.y = az_relu(fmaf(x.y, isc.y, ish.y));
+                        x.z = az_relu(fmaf(x.z, isc.z, ish.z)); x.w = az_relu(fmaf(x.w, isc.w, ish.w));
                     }
                 }
                 x01[j] = c1_f2{x.x, x.y}; x23[j] = c1_f2{x.z, x.w};

@@ -37,6 +37,9 @@ disp_loss_fwd_kernel(double *__restrict__ acc, const float *__restrict__ p3, con
     dl_flush<4>(v, acc);
 }
 
+// clamp(d, -1, 1) that keeps a NaN, as the autograd gradient of smooth-L1 does (fminf / fmaxf would give -1)
+__device__ __forceinline__ float dl_clamp1(float d) { return az_min_nan(az_max_nan(d, -1.f), 1.f); }
+
 // d loss / d pred_k = w_k * gloss / count * clamp(pred_k - gt, -1, 1) on valid pixels, 0 elsewhere
 __global__ void __launch_bounds__(DL_BLOCK)
 disp_loss_bwd_kernel(float *__restrict__ g3, float *__restrict__ g2, float *__restrict__ g1,
@@ -48,9 +51,9 @@ disp_loss_bwd_kernel(float *__restrict__ g3, float *__restrict__ g2, float *__re
     for (long long i = (long long)blockIdx.x * DL_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * DL_BLOCK) {
         const float g = gt[i];
         const bool ok = dl_valid(mask, g, lo, hi, i);
-        g3[i] = ok ? w3 * s * fminf(fmaxf(p3[i] - g, -1.f), 1.f) : 0.f;
-        g2[i] = ok ? w2 * s * fminf(fmaxf(p2[i] - g, -1.f), 1.f) : 0.f;
-        g1[i] = ok ? w1 * s * fminf(fmaxf(p1[i] - g, -1.f), 1.f) : 0.f;
+        g3[i] = ok ? w3 * s * dl_clamp1(p3[i] - g) : 0.f;
+        g2[i] = ok ? w2 * s * dl_clamp1(p2[i] - g) : 0.f;
+        g1[i] = ok ? w1 * s * dl_clamp1(p1[i] - g) : 0.f;
     }
 }
 
@@ -70,7 +73,7 @@ disp_metrics_kernel(double *__restrict__ acc, const float *__restrict__ disp_gt,
         const float zp = depth_pred ? depth_pred[i] : fb[i / per_batch] / dp;
         const float zg = depth_gt[i];
         const float dz = fabsf(zg - zp);
-        const float dmm = fminf(fmaxf(fabsf(zg * 1000.f - zp * 1000.f), 0.f), 100.f);
+        const float dmm = az_min_nan(az_max_nan(fabsf(zg * 1000.f - zp * 1000.f), 0.f), 100.f);  // torch.clip: NaN stays, inf -> 100
         v[0] += dd;
         v[1] += dd > 1.f ? 1.0 : 0.0;
         v[2] += dd > 2.f ? 1.0 : 0.0;

@@ -12,7 +12,7 @@ __device__ __forceinline__ void az_store_affine(float *outp, const float *resp, 
                                                 int relu) {
     float y = acc * sc + sf;
     if (resp) y += resp[off];
-    if (relu) y = fmaxf(y, 0.f);
+    if (relu) y = az_relu(y);
     outp[off] = y;
 }
 

@@ -104,7 +104,8 @@ __device__ __forceinline__ float4 az_roll_affine_fma(const f32x4 v, const float4
     return make_float4(fmaf(v[0], sc.x, sf.x), fmaf(v[1], sc.y, sf.y), fmaf(v[2], sc.z, sf.z), fmaf(v[3], sc.w, sf.w));
 }
 
-// the finish of one 16-byte piece: + residual (RES; read at roff), floor (FLOOR: 0 for a ReLU, -inf for none), store at off;
+// the finish of one 16-byte piece: + residual (RES; read at roff), floor (FLOOR: 0 for a ReLU, -inf for none; a NaN stays NaN
+// under either, az_max_nan), store at off;
 // offsets are R_OOB in the lanes whose voxel is outside.  Returns what it stored.
 template <bool RES, bool FLOOR>
 __device__ __forceinline__ float4 az_roll_finish_piece(float4 y, az_rsrc rs_res, unsigned roff, float floor_, az_rsrc rs_out, unsigned off) {
@@ -112,7 +113,7 @@ __device__ __forceinline__ float4 az_roll_finish_piece(float4 y, az_rsrc rs_res,
         const float4 rr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_res, roff, 0, 0));
         y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
     }
-    if (FLOOR) { y.x = fmaxf(y.x, floor_); y.y = fmaxf(y.y, floor_); y.z = fmaxf(y.z, floor_); y.w = fmaxf(y.w, floor_); }
+    if (FLOOR) { y.x = az_max_nan(y.x, floor_); y.y = az_max_nan(y.y, floor_); y.z = az_max_nan(y.z, floor_); y.w = az_max_nan(y.w, floor_); }
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y), rs_out, off, 0, 0);
     return y;
 }

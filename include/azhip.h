@@ -212,7 +212,17 @@ int az_conv3d_wgrad(float *grad_w, float *workspace, long long workspace_bytes,
  *     65504).  AZ_DEBUG_AMAX=1 makes the Python wrappers check every attached amax against a fresh az_absmax
  *     (synchronising) and name the tensor.  A saturating conversion (MODE.FP16_OVFL) is deliberately not used: on gfx950
  *     the same bit makes the fp16 MFMA clamp inf operands to FLT_MAX and drop NaN operands (tools/probes/fp16_ovfl_probe.hip).
- * az_absmax: the amax array of x (16-byte aligned; n > 0), zeroing included. */
+ * az_absmax: the amax array of x (16-byte aligned; n > 0), zeroing included.
+ *
+ * Non-finite values.  A NaN read by an output is a NaN in that output, through every fused activation of this header: the
+ * ReLU and the residual sum of the BatchNorm apply kernels, of az_add_relu and of every convolution epilogue (with the ReLU
+ * off as well: an input-gradient launch returns NaN, not -inf), the fused relu(in * scale + shift) operand of the 32 -> 1
+ * kernels, the gradient clamp of az_disp_loss_bwd and the millimetre clip of az_disp_metrics.  A NaN in a train-mode
+ * BatchNorm's input makes its channel's mean, invstd, scale, shift and running statistics NaN, and with them the whole
+ * output channel.  What an inf becomes is the reference's point-wise result -- relu(-inf) = 0, relu(+inf) = +inf,
+ * clip(inf, 0, 100) = 100 -- except inside an f16x3 product, where the paragraph above holds (an inf operand may come out
+ * as NaN).  An output that reads nothing non-finite holds the bits it holds without the bad element elsewhere in the
+ * tensor (tests/test_gpu_nonfinite.py). */
 #define AZ_AMAX_SLOTS 16
 #define AZ_AMAX_STRIDE 64
 #define AZ_AMAX_FLOATS (AZ_AMAX_SLOTS * AZ_AMAX_STRIDE)

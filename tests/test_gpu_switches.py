@@ -110,6 +110,14 @@ REPROJ_CASES = [
 ]
 
 
+# The non-finite sweep (tests/test_gpu_nonfinite.py) on the one forward route that only a switch reaches: the bf16x6 32-channel
+# stride-1 layers on az_conv3d_m128.hip; that file's route-coverage test asserts under the switch that they are there.
+NONFINITE = "tests/test_gpu_nonfinite.py"
+NONFINITE_CASES = [
+    ({"AZ_CONV_ROLL": "0"}, NONFINITE, "conv3d_s1 and bf16x6 or every_forward_route or rolling_kernels"),
+]
+
+
 def _child(env, path, expr):
     cmd = [sys.executable, "-m", "pytest", path, "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider"]
     if expr:
@@ -142,6 +150,11 @@ def test_strided_sweep_behind_switch(env, path, expr):
 
 @pytest.mark.parametrize("env,path,expr", REPROJ_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in REPROJ_CASES])
 def test_reprojection_sweep_behind_switch(env, path, expr):
+    _child(env, path, expr)
+
+
+@pytest.mark.parametrize("env,path,expr", NONFINITE_CASES, ids=[" ".join(f"{k}={v}" for k, v in c[0].items()) for c in NONFINITE_CASES])
+def test_nonfinite_sweep_behind_switch(env, path, expr):
     _child(env, path, expr)
 
 
