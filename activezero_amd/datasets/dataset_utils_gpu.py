@@ -4,7 +4,9 @@ batch is processed on the device by az_ir_pattern (csrc/az_ir_pattern.hip).  get
 reference's offline tool tools/temporal_ir.py (csrc/az_temporal_ir.hip): the pattern of a real view from its stack of
 projector exposures, made per item on the device instead of by a pass over the dataset before training.
 augment_images / data_augmentation are the twin of data_augmentation (dataset_utils.py:49-83: GaussianBlur, ColorJitter,
-ToTensor, Normalize) on az_augment (csrc/az_augment.hip): a batch of grey images in, normalised 3-channel images out."""
+ToTensor, Normalize) on az_augment (csrc/az_augment.hip): a batch of grey images in, normalised 3-channel images out.
+resize_bilinear is the twin of the PIL resize the real item goes through (messytable.py:324-341, 353-356, 410-420) on
+az_resize_bilinear_u8 (csrc/az_resample.hip): 8-bit grey images in, PIL's bits out, cropped on the way if asked."""
 import torch
 
 from activezero_amd import _lib
@@ -126,6 +128,66 @@ def augment_images(grey, sigma=None, brightness=None, contrast=None, contrast_fi
     with torch.cuda.device(g.device):
         _call("az_augment", _p(out), _p(ws), ws_bytes, _p(g), int(g.dtype == torch.uint8), _p(params), n, h, w,
               int(kernel_size), flags, _stream())
+    return out[0] if grey.dim() == 2 else out
+
+
+_RESAMPLE_TABLES = {}  # (in_size, out_size, device) -> [out_size, 2 + ksize] int32 on the device
+
+
+def _resample_ksize(in_size, out_size, what):
+    """taps per table row for one axis, from the library's host function; raises for a size it refuses"""
+    ks = _lib.lib().az_resample_bilinear_ksize(int(in_size), int(out_size))
+    if ks == _lib.CONST["AZ_EUNSUPPORTED"]:
+        raise RuntimeError(f"resize_bilinear: {what} {in_size} -> {out_size}: a ratio above 8 is not supported")
+    if ks < 0:
+        raise RuntimeError(f"resize_bilinear: {what} {in_size} -> {out_size}: sizes must be positive")
+    return ks
+
+
+def _resample_table(in_size, out_size, device):
+    """the device copy of the library's coefficient table for one axis: built on the host and copied once per
+    (in, out, device), then served from the cache"""
+    key = (int(in_size), int(out_size), torch.device(device))
+    table = _RESAMPLE_TABLES.get(key)
+    if table is None:
+        ks = _resample_ksize(in_size, out_size, "size")
+        host = torch.empty(key[1], 2 + ks, dtype=torch.int32)
+        _call("az_resample_bilinear_table", host.data_ptr(), key[0], key[1])
+        table = _RESAMPLE_TABLES[key] = host.to(key[2])
+    return table
+
+
+def resize_bilinear(grey, size, crop=None, dtype=torch.uint8):
+    """PIL's Image.resize(size, resample=Image.BILINEAR) on 8-bit grey images, bit for bit (messytable.py:324-341, 353-356,
+    410-420), for a [Hin,Win] or [B,Hin,Win] uint8 CUDA tensor; size = (Hout, Wout) -- rows first, where PIL takes
+    (width, height).  crop = (y0, x0, h, w) returns only that window of the resized image (messytable.py:366-398), None the
+    whole image.  dtype torch.uint8 gives the levels, torch.float32 the image v / 255 with the bits of
+    torch.from_numpy(np.array(img) / 255).float().  Returns [h,w] or [B,h,w].  Sizes with in > 8 out are refused (unless in <= 17).  The two
+    coefficient tables come from the library and are cached on the device per (in, out, device): the first call for a size
+    pair copies them, every later call is one launch and synchronises nothing."""
+    if not isinstance(grey, torch.Tensor):
+        raise TypeError("grey: expected a tensor")
+    if grey.dim() not in (2, 3):
+        raise RuntimeError("grey must be [Hin,Win] or [B,Hin,Win]")
+    if grey.dtype != torch.uint8:
+        raise RuntimeError(f"grey: expected torch.uint8, got {grey.dtype}")
+    if dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f"dtype: expected torch.uint8 or torch.float32, got {dtype}")
+    hin, win = grey.shape[-2:]
+    hout, wout = (int(s) for s in size)
+    _resample_ksize(hin, hout, "height")
+    _resample_ksize(win, wout, "width")
+    y0, x0, h, w = (0, 0, hout, wout) if crop is None else (int(c) for c in crop)
+    if y0 < 0 or x0 < 0 or h <= 0 or w <= 0 or y0 + h > hout or x0 + w > wout:
+        raise RuntimeError(f"crop {(y0, x0, h, w)} lies outside the {hout} x {wout} image")
+    g = _chk((grey[None] if grey.dim() == 2 else grey).contiguous(), "grey", torch.uint8)
+    n = g.shape[0]
+    table_y, table_x = _resample_table(hin, hout, g.device), _resample_table(win, wout, g.device)
+    out = torch.empty(n, h, w, dtype=dtype, device=g.device)
+    u8, f32 = (out, None) if dtype == torch.uint8 else (None, out)
+    with torch.cuda.device(g.device):
+        _call("az_resize_bilinear_u8", _p(u8), _p(f32), _p(g), _p(table_y), _p(table_x), n, hin, win, hout, wout, y0, x0,
+              h, w, _stream())
     return out[0] if grey.dim() == 2 else out
 
 

@@ -18,6 +18,19 @@ runs end to end without the dataset:
                                              (messytable.py:264-270: one drawn sigma, brightness and contrast for both
                                              views; configs/config.py:104-113), on the device; the real images keep the
                                              normalisation only (messytable.py:402-404)
+  (real_size=(Hr, Wr))                       the real views are rendered at Hr x Wr, quantised to uint8 levels
+                                             (round(255 x)) and brought to H x W = (int(0.75 Hr), int(0.75 Wr)) by
+                                             resize_bilinear, PIL's 8-bit BILINEAR resize on the device, as
+                                             messytable.py:324-341 takes its 720 x 1280 captures to 540 x 960: img_real_L / R
+                                             are augment_images of the resized levels (normalisation only), the patterns
+                                             come from the resized float images; with temporal=True the exposure stack is
+                                             rendered at Hr x Wr, get_temporal_ir_pattern runs there and its 0 / 1 pattern
+                                             is resized as levels 0 / 255 to float32, as messytable.py:410-420 resizes
+                                             the stored pattern -- values in [0,1], no longer binary.  (The reference's
+                                             stored pattern is a PNG that tools/temporal_ir.py wrote through matplotlib's
+                                             colour map and that the loader converts from RGB back to grey before the
+                                             resize; that round trip is not reproduced.)  Keys, shapes and dtypes are
+                                             those of the default, which renders the real views at H x W directly.
 
 Geometry: a smooth random depth field -> disparity = focal * baseline / depth; the right view is the left one
 moved by the (integer-rounded) disparity with the scatter warp K1, so disparity, images and patterns are
@@ -25,8 +38,8 @@ mutually consistent and the losses have signal."""
 import torch
 import torch.nn.functional as F
 
-from activezero_amd.datasets.dataset_utils_gpu import (data_augmentation, get_smoothed_ir_pattern2,
-                                                       get_temporal_ir_pattern)
+from activezero_amd.datasets.dataset_utils_gpu import (augment_images, data_augmentation, get_smoothed_ir_pattern2,
+                                                       get_temporal_ir_pattern, resize_bilinear)
 from activezero_amd.utils.warp_ops import apply_disparity_cu
 
 _MEAN = (0.485, 0.456, 0.406)
@@ -35,9 +48,13 @@ _STD = (0.229, 0.224, 0.225)
 
 class SyntheticMessytableDataset(torch.utils.data.Dataset):
     def __init__(self, length=64, height=256, width=512, onReal=True, device="cuda:0", seed=0, max_disp=192,
-                 temporal=False, augment=False):
+                 temporal=False, augment=False, real_size=None):
         self.temporal, self.augment = bool(temporal), bool(augment)
         self.length, self.h, self.w, self.onReal = int(length), int(height), int(width), bool(onReal)
+        self.real_size = None if real_size is None else (int(real_size[0]), int(real_size[1]))
+        if self.real_size is not None and (int(self.real_size[0] * 0.75), int(self.real_size[1] * 0.75)) != (self.h, self.w):
+            raise RuntimeError(f"real_size {self.real_size} scaled by 0.75 (messytable.py:324-341) is not "
+                               f"(height, width) = {(self.h, self.w)}")
         self.device, self.seed, self.max_disp = torch.device(device), int(seed), int(max_disp)
         self.focal_length, self.baseline = 446.31, 0.055  # the order of the MessyTable rig (metres, half-res pixels)
 
@@ -51,9 +68,10 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
         low = torch.rand(1, 1, cells, 2 * cells, device=self.device, generator=g)
         return F.interpolate(low, size=(h, w), mode="bicubic", align_corners=False).clamp(0, 1)[0, 0]
 
-    def _views(self, g):
-        """(left, right) grey images with IR dots, their no-IR versions, left/right disparity at 2x resolution"""
-        h, w = self.h, self.w
+    def _views(self, g, size=None):
+        """(left, right) grey images with IR dots, their no-IR versions, left/right disparity at 2x resolution; at
+        `size` = (h, w) instead of the item's"""
+        h, w = (self.h, self.w) if size is None else size
         depth2 = 0.45 + 1.1 * self._smooth(g, 2 * h, 2 * w, 6)             # metres, 2x resolution
         disp2 = self.focal_length * self.baseline / depth2                 # half-res pixels (messytable.py:205-213)
         disp = F.avg_pool2d(disp2[None, None], 2)[0, 0]
@@ -75,9 +93,10 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
         return ((rgb - mean) / std).contiguous()
 
     def _real_views(self, idx):
-        """the real item's generator, noisy (left, right), their no-IR versions and the noise-free lit pair [2,H,W]"""
+        """the real item's generator, noisy (left, right), their no-IR versions and the noise-free lit pair [2,H,W]; at
+        real_size when one is set"""
         g = self._gen(idx, 2)
-        rl, rr, rl0, rr0, *_ = self._views(g)
+        rl, rr, rl0, rr0, *_ = self._views(g, self.real_size)
         lit = torch.stack([rl, rr])
         noise = lambda im: (im + 0.02 * torch.randn(im.shape, device=self.device, generator=g)).clamp(0, 1)
         return g, noise(rl), noise(rr), rl0, rr0, lit
@@ -93,6 +112,30 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
         """the exposure stack item `idx` takes its real patterns from (temporal=True); for tests"""
         g, _, _, rl0, rr0, lit = self._real_views(idx)
         return self._exposures(g, lit, torch.stack([rl0, rr0]))
+
+    @staticmethod
+    def _levels(x):
+        """[0,1] images as uint8 grey levels, what a sensor stores"""
+        return (255.0 * x).round().clamp(0, 255).to(torch.uint8)
+
+    def _real_levels(self, idx):
+        """[4,Hr,Wr] uint8: the levels item `idx` resizes (real_size set) -- left, right and their no-IR versions; for tests"""
+        _, rl, rr, rl0, rr0, _ = self._real_views(idx)
+        return self._levels(torch.stack([rl, rr, rl0, rr0]))
+
+    def _real_resized(self, g, rl, rr, rl0, rr0, lit):
+        """the real entries of an item whose views were rendered at real_size: everything passes through resize_bilinear"""
+        size = (self.h, self.w)
+        levels = self._levels(torch.stack([rl, rr, rl0, rr0]))
+        real = augment_images(resize_bilinear(levels[:2], size))
+        if self.temporal:
+            native = get_temporal_ir_pattern(self._exposures(g, lit, torch.stack([rl0, rr0])))
+            rpat = resize_bilinear((255.0 * native).to(torch.uint8), size, dtype=torch.float32)
+        else:
+            grey = resize_bilinear(levels, size, dtype=torch.float32)
+            rpat = get_smoothed_ir_pattern2(grey[:2], grey[2:])
+        return {"img_real_L": real[0].contiguous(), "img_real_R": real[1].contiguous(),
+                "img_real_L_reproj": rpat[0:1].contiguous(), "img_real_R_reproj": rpat[1:2].contiguous()}
 
     def _augmentation(self, idx):
         return data_augmentation(True, True, generator=self._gen(idx, 3))
@@ -122,6 +165,9 @@ class SyntheticMessytableDataset(torch.utils.data.Dataset):
             item["img_sim_L"], item["img_sim_R"] = pair[0].contiguous(), pair[1].contiguous()
         if self.onReal:
             g, rl, rr, rl0, rr0, lit = self._real_views(idx)
+            if self.real_size is not None:
+                item.update(self._real_resized(g, rl, rr, rl0, rr0, lit))
+                return item
             if self.temporal:
                 rpat = get_temporal_ir_pattern(self._exposures(g, lit, torch.stack([rl0, rr0])))
             else:

@@ -645,6 +645,35 @@ long long az_augment_workspace(int B, int H, int W, int ks);
 int az_augment(float *out, float *workspace, long long workspace_bytes, const void *img, int img_is_u8,
                const float *params, int B, int H, int W, int ks, int flags, void *stream);
 
+/* ---- K21: the real domain's resize, bit for bit Pillow's (data side; az_resample.hip) ---------
+ * replaces Image.resize(size, resample=Image.BILINEAR) on 8-bit grey images as datasets/messytable.py:324-341 (the real
+ * images), :353-356 (the robot mask) and :410-420 (the stored temporal pattern) call it, 720 x 1280 -> 540 x 960.  Pillow's
+ * 8-bit path is fixed-point, two passes with a ROUNDED uint8 IMAGE BETWEEN THEM, horizontal first:
+ *   pass      v = clamp(((1 << 21) + sum_k pixel[first + k] * coef[k]) >> 22, 0, 255), int32, k < count
+ *   tables    per axis and output index the triangle filter of support max(in / out, 1): first, count and the weights
+ *             normalised to sum 1, each rounded to (int)(0.5 + w * 2^22); every step in double, in Pillow's order
+ *             (az_resample_table.h).  ksize = (int)ceil(max(in / out, 1)) * 2 + 1 taps per row, at most 17; in == out
+ *             gives the identity.
+ * The tables are built on the HOST: az_resample_bilinear_ksize returns the taps per row, az_resample_bilinear_table
+ * writes table [out_size, 2 + ksize] int32 (first, count, coef[0 .. ksize), zero from count on) into host memory; no
+ * stream, no device.  1 <= in_size <= 8 out_size, else AZ_EUNSUPPORTED -- but for an axis of at most 17 pixels, which is
+ * taken at any ratio: count <= in_size, so its rows fit the 17 taps of the cap, and its table has ksize 17; a non-positive
+ * size or a null table: AZ_EINVAL.
+ * az_resize_bilinear_u8: img [N,Hin,Win] uint8; table_y / table_x: DEVICE copies of the tables for Hin -> Hout and
+ * Win -> Wout; the window [y0, y0 + h) x [x0, x0 + w) of the Hout x Wout result (the loader's crop, messytable.py:366-398,
+ * costs nothing) is written, fully, as out_u8 [N,h,w] levels and / or out_f32 [N,h,w] = v / 255 with a correctly rounded
+ * fp32 division -- the bits of float32(float64(v) / 255), what np.array(img) / 255 becomes as a float tensor; either
+ * pointer may be NULL, not both.  One launch, integer arithmetic in a fixed order: the same bits from run to run.
+ * The device cannot be asked about a table's contents before the launch, so the kernel clamps every source index: a
+ * corrupt table gives wrong pixels, never a read outside img.
+ * img or a table null, both outputs null, a non-positive size, a window outside [0, Hout) x [0, Wout): AZ_EINVAL; a
+ * ratio above 8 on an axis of more than 17 pixels, N > 65535 or Hin * Win >= 2^31: AZ_EUNSUPPORTED; all before any launch. */
+int az_resample_bilinear_ksize(int in_size, int out_size);
+int az_resample_bilinear_table(int32_t *table, int in_size, int out_size);
+int az_resize_bilinear_u8(uint8_t *out_u8, float *out_f32, const uint8_t *img, const int32_t *table_y,
+                          const int32_t *table_x, int N, int Hin, int Win, int Hout, int Wout, int y0, int x0, int h,
+                          int w, void *stream);
+
 /* ---- K10/K11: RAFT-Stereo 1-D correlation (secondary path) -----------------------
  * replaces nets/raft/corr.py:115-161 (CorrBlock1D: einsum all-pairs correlation /
  * sqrt(C), avg_pool pyramid over the last axis, 2r+1-tap linear lookup through

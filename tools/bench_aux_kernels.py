@@ -22,7 +22,13 @@ utils/util.py:185-244): a recorded measurement, not a product path.
     python tools/bench_aux_kernels.py augment [out.json]
 times the loader's blur + colour jitter + normalisation (K20, both stages on, ks = 9) at B = 8, 540x960 and at the training
 crop 256x512, for uint8 and float32 images: the kernel pair, the copy probe moving the same algorithmic bytes, and the plain
-torch fp32 operator chain (reflect F.pad, F.conv2d with the 2-D kernel, the blends, the normalisation) on the same inputs."""
+torch fp32 operator chain (reflect F.pad, F.conv2d with the 2-D kernel, the blends, the normalisation) on the same inputs.
+
+    python tools/bench_aux_kernels.py resize [out.json]
+times the real domain's resize (K21, Pillow's 8-bit BILINEAR, bit for bit) at B = 8, 720x1280 -> 540x960, whole and with the
+256x512 crop (100, 200), for uint8 and float32 output: the kernel, the copy probe (az_hbm_copy_probe) moving the same
+algorithmic bytes, and F.interpolate(mode="bilinear", antialias=True) on the float image (cropped afterwards) -- the nearest
+stock operator, which is not bit-compatible; the record says how many levels differ."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -270,6 +276,80 @@ def augment(out_path=None):
             fh.write(json.dumps(rec, indent=1) + "\n")
 
 
+def resize(out_path=None):
+    import json
+    import statistics
+    import torch.nn.functional as F
+    from activezero_amd import ops
+    from activezero_amd.datasets import dataset_utils_gpu as du
+    dev = torch.device("cuda:0")
+    B, Hin, Win, Hout, Wout, reps = 8, 720, 1280, 540, 960, 20
+    g = torch.Generator(device=dev).manual_seed(0)
+    rec = {"case": "resize", "batch": B, "in": [Hin, Win], "out": [Hout, Wout],
+           "timing": "one call per buffer set, the sets rotated (together more than the 256 MiB cache), per event pair; "
+                     "median of %d after two warm-up rounds; the copy probe moves the same number of bytes (half in, half "
+                     "out) through the same rotation" % reps}
+
+    def events(fn, sets):
+        for _ in range(2):
+            for i in range(sets):
+                fn(i)
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(sets):
+                fn(i)
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / sets)
+        return statistics.median(ms), min(ms)
+
+    ty, tx = du._resample_table(Hin, Hout, dev), du._resample_table(Win, Wout, dev)
+    for window in ((0, 0, Hout, Wout), (100, 200, 256, 512)):
+        y0, x0, h, w = window
+        # source rows / columns the window's taps span: what a cropped call has to read
+        ylo, yhi = int(ty[y0, 0]), int(ty[y0 + h - 1, 0] + ty[y0 + h - 1, 1])
+        xlo, xhi = int(tx[x0, 0]), int(tx[x0 + w - 1, 0] + tx[x0 + w - 1, 1])
+        for name, dtype, size in (("u8", torch.uint8, 1), ("f32", torch.float32, 4)):
+            nbytes = float(B) * ((yhi - ylo) * (xhi - xlo) + h * w * size)
+            per_set = B * (Hin * Win + h * w * size)
+            sets = max(8, -(-300 * (1 << 20) // per_set))
+            imgs = [torch.randint(0, 256, (B, Hin, Win), device=dev, generator=g, dtype=torch.uint8) for _ in range(sets)]
+            outs = [torch.empty(B, h, w, dtype=dtype, device=dev) for _ in range(sets)]
+
+            def launch(i):
+                ops._call("az_resize_bilinear_u8", outs[i].data_ptr() if size == 1 else None,
+                          outs[i].data_ptr() if size == 4 else None, imgs[i].data_ptr(), ty.data_ptr(), tx.data_ptr(), B, Hin,
+                          Win, Hout, Wout, y0, x0, h, w, ops._stream())
+
+            def stock(i):  # the nearest stock operator: not bit-compatible with Pillow's fixed-point passes
+                x = F.interpolate((imgs[i].float() / 255)[:, None], size=(Hout, Wout), mode="bilinear", antialias=True,
+                                  align_corners=False)[:, 0, y0:y0 + h, x0:x0 + w]
+                return (255 * x).round().to(torch.uint8) if size == 1 else x.contiguous()
+
+            launch(0)
+            assert torch.equal(outs[0], du.resize_bilinear(imgs[0], (Hout, Wout), crop=window, dtype=dtype))
+            diff = (outs[0].float() * (1 if size == 1 else 255) - stock(0).float() * (1 if size == 1 else 255)).abs()
+            m, lo = events(launch, sets)
+            sm, slo = events(stock, sets)
+            nf = int(nbytes) // 8  # floats the probe copies: 4 bytes in + 4 bytes out each
+            src = [torch.empty(nf, device=dev).normal_() for _ in range(sets)]
+            dst = [torch.empty(nf, device=dev) for _ in range(sets)]
+            pm, plo = events(lambda i: ops._call("az_hbm_copy_probe", dst[i].data_ptr(), src[i].data_ptr(), nf, ops._stream()),
+                             sets)
+            rec["%dx%d_%s" % (h, w, name)] = {
+                "window": list(window), "ms": m, "min_ms": lo, "algorithmic_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6,
+                "copy_probe_ms_same_bytes": pm, "copy_probe_min_ms": plo, "of_copy_probe": pm / m,
+                "interpolate_antialias_ms": sm, "interpolate_antialias_min_ms": slo, "speedup_vs_interpolate": sm / m,
+                "levels_differing_from_interpolate": float((diff >= 0.5).float().mean()),
+                "max_level_diff_vs_interpolate": float(diff.max()), "buffer_sets": sets}
+            del imgs, outs, src, dst
+    print(json.dumps(rec))
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(rec, indent=1) + "\n")
+
+
 def _write_case(rec, out_path):
     """print the record; merge it into out_path under its case name"""
     import json
@@ -430,6 +510,9 @@ if len(sys.argv) > 1 and sys.argv[1] in ("gt_prep", "error_img"):
     sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "augment":
     augment(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "resize":
+    resize(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "temporal_ir":
     temporal_ir(sys.argv[2] if len(sys.argv) > 2 else None)
