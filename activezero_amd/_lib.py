@@ -106,7 +106,7 @@ def parse_header(text):
 # _RESTYPE), the integer AZ_* constants, and the descriptor structs as numpy dtypes, all read from it once, here
 with open(HEADER) as _f:
     _SIGS, _RESTYPE, CONST, _STRUCTS = parse_header(_f.read())
-PACK_DESC, UNPACK_DESC = _STRUCTS["AzPackDesc"], _STRUCTS["AzUnpackDesc"]
+PACK_DESC, UNPACK_DESC, ABSMAX_DESC = _STRUCTS["AzPackDesc"], _STRUCTS["AzUnpackDesc"], _STRUCTS["AzAbsmaxDesc"]
 
 
 def declared_symbols():

@@ -6,15 +6,16 @@ This module owns how an amax gets to the launch that needs it:
     backward, residual sums, through a pre-zeroed array from ZEROS) and valid while the tensor's version counter stands
     (_set_amax / _get_amax); absmax() takes it with a pass of az_absmax when nobody attached one;
   * weights get theirs once per version -- once per optimizer step -- from the cache behind weight_amax(), which
-    prime_weight_amax() fills for a whole model in three launches.
+    prime_weight_amax() fills for a whole model in one call of az_absmax_multi.
 """
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import profiler
-from ._lib import CONST
+from ._lib import ABSMAX_DESC, CONST
 from .ops import _call, _p, _stream
 
 AMAX_SLOTS = CONST["AZ_AMAX_FLOATS"]  # floats of an "amax array" (include/azhip.h: 16 slots, 256 bytes apart)
@@ -113,18 +114,63 @@ def weight_amax(weight, w):
     return am
 
 
+def absmax_tables(rows):
+    """launch_tables (packing.py) of az_absmax_multi: one descriptor per tensor, dicts with src, amax, n"""
+    from .packing import launch_tables
+    return launch_tables(ABSMAX_DESC, rows, lambda r: r["n"])
+
+
+class MultiAbsmax:
+    """az_absmax_multi (include/azhip.h) for sets of tensors that come back step after step: the amax arrays of all of them
+    in one call -- the largest FINITE magnitude of each, the bits az_absmax gives, where a max-norm of the tensor would be
+    inf / NaN after one bad element and flush every finite weight to zero (az_common.h).  The device tables of a set are
+    uploaded once (the only blocking copy) and found again by the addresses and lengths they describe, so they stay right
+    for whatever tensor lives at those addresses; the caller keeps the amax arrays alive."""
+
+    def __init__(self, limit=8):
+        self.tables, self.limit = {}, limit
+
+    def clear(self):
+        self.tables.clear()
+
+    def run(self, tensors, rows):
+        """rows[i] (an amax array, any content) <- the amax array of tensors[i] (contiguous fp32 on one device)"""
+        dev = tensors[0].device
+        key = tuple((t.data_ptr(), t.numel(), r.data_ptr()) for t, r in zip(tensors, rows))
+        tab = self.tables.get(key)
+        if tab is None:
+            descs, block_desc, first, nblocks = absmax_tables([dict(src=p, amax=a, n=n) for p, n, a in key])
+            if len(self.tables) >= self.limit:
+                self.tables.clear()
+            tab = self.tables[key] = (torch.from_numpy(descs.view(np.uint8)).to(dev), torch.from_numpy(block_desc).to(dev),
+                                      torch.from_numpy(first).to(dev), len(key), nblocks)
+        descs, block_desc, first, nd, nblocks = tab
+        with torch.cuda.device(dev), profiler.scope("absmax", bytes=4.0 * sum(k[1] for k in key), bound="hbm"):
+            _call("az_absmax_multi", _p(descs), _p(block_desc), _p(first), nd, nblocks, _stream())
+
+
+_PRIME = MultiAbsmax()
+_PRIME_ROWS = {}  # (device index, ((data_ptr, numel), ...)) -> the [len, AMAX_SLOTS] arrays of that set of weights
+
+
 def prime_weight_amax(weights):
-    """The amax arrays of all given weight tensors in THREE launches (one multi-tensor max-norm, one stack, one scatter
-    into zeroed arrays) instead of a memset + reduction per weight and step: fills the per-version cache that the f16x3
-    packers read.  Weights whose current version is already cached are skipped; called at the start of a forward pass."""
+    """The amax arrays of all given weight tensors in ONE call of az_absmax_multi instead of a memset + reduction per weight
+    and step: fills the per-version cache that the f16x3 packers read.  Weights whose current version is already cached are
+    skipped; called at the start of a forward pass.  A set of weights keeps its arrays from step to step (rewritten in
+    stream order, as the rows of packing.PackPlan are), so that the call's device tables are uploaded once per set."""
     with _W_LOCK:
-        todo = [w for w in weights if w is not None and w.is_cuda and w.dtype == torch.float32 and _w_key(w) not in _W_AMAX]
-    if not todo:
-        return
-    with torch.no_grad():
-        dets = [w.detach() for w in todo]
-        maxes = torch.stack(torch._foreach_norm(dets, float("inf")))
-        arr = torch.zeros(len(todo), AMAX_SLOTS, dtype=torch.float32, device=dets[0].device)
-        arr[:, 0] = maxes
+        todo = [w for w in weights if w is not None and w.is_cuda and w.dtype == torch.float32 and w.numel() > 0
+                and _w_key(w) not in _W_AMAX]
+        if not todo:
+            return
+        dets = [w.detach().contiguous() for w in todo]
+        key = (dets[0].device.index, tuple((d.data_ptr(), d.numel()) for d in dets))
+        arr = _PRIME_ROWS.get(key)
+        if arr is None:
+            if len(_PRIME_ROWS) >= _PRIME.limit:
+                _PRIME_ROWS.clear()
+                _PRIME.clear()
+            arr = _PRIME_ROWS[key] = torch.empty(len(todo), AMAX_SLOTS, dtype=torch.float32, device=dets[0].device)
+        _PRIME.run(dets, list(arr))
     for i, w in enumerate(todo):
         remember_weight_amax(w, arr[i])

@@ -36,3 +36,33 @@ extern "C" int az_absmax(float *amax, const float *x, long long n, void *stream)
                        reinterpret_cast<unsigned *>(amax), x, n);
     return az_launch_status();
 }
+
+// ---- the amax arrays of many tensors in one call (include/azhip.h; the weights of a model, once per optimizer step) ------
+// built like az_pack_f16_multi (az_misc.hip): one workgroup per 256-element chunk of ONE tensor, found through block_desc /
+// first_block, and one conditional atomic per workgroup into that tensor's array (az_amax_flush).  The arrays are zeroed by a
+// kernel over the same descriptors first: they need not be contiguous (packing.py keeps persistent rows).
+__global__ void __launch_bounds__(256)
+absmax_multi_zero_kernel(const AzAbsmaxDesc *__restrict__ descs) {
+    float *row = descs[blockIdx.x].amax;
+    for (int i = threadIdx.x; i < AZ_AMAX_FLOATS; i += 256) row[i] = 0.f;
+}
+
+__global__ void __launch_bounds__(256)
+absmax_multi_kernel(const AzAbsmaxDesc *__restrict__ descs, const int *__restrict__ block_desc, const int *__restrict__ first_block) {
+    const int di = block_desc[blockIdx.x];
+    const AzAbsmaxDesc d = descs[di];  // (block-uniform: scalar loads)
+    const long long idx = (long long)(blockIdx.x - first_block[di]) * 256 + threadIdx.x;
+    const unsigned m = idx < d.n ? az_finite_abs_bits(d.src[idx]) : 0u;
+    az_amax_flush(reinterpret_cast<unsigned *>(d.amax), m);
+}
+
+extern "C" int az_absmax_multi(const AzAbsmaxDesc *descs, const int *block_desc, const int *first_block, int nd, int nblocks,
+                               void *stream) {
+    AZ_REQUIRE_PTR(descs); AZ_REQUIRE_PTR(block_desc); AZ_REQUIRE_PTR(first_block);
+    AZ_REQUIRE(nd > 0 && nblocks > 0);
+    hipStream_t s = az_stream(stream);
+    hipLaunchKernelGGL(absmax_multi_zero_kernel, dim3((unsigned)nd), dim3(256), 0, s, descs);
+    if (az_launch_status() != AZ_OK) return AZ_ELAUNCH;
+    hipLaunchKernelGGL(absmax_multi_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, descs, block_desc, first_block);
+    return az_launch_status();
+}

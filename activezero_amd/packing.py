@@ -119,6 +119,7 @@ class PackPlan:
         self.table = None      # (descs, block_desc, first_block, nd, nblocks, entry list) on the device: the last one used
         self.tables = {}       # tuple of registered addresses -> table + the amax pointers it was built with
         self.launches = 0      # az_pack_f16_multi launches so far (tests)
+        self.amax_op = amax.MultiAbsmax()  # az_absmax_multi and its device tables, per set of stale weights
 
     # -- weight amax rows: persistent, so that the descriptor table stays valid across steps
     def amax_row(self, w):
@@ -147,6 +148,7 @@ class PackPlan:
             self.entries = {k: e for k, e in self.entries.items() if k[0] not in dead}
             self.table = None
             self.tables.clear()
+            self.amax_op.clear()
 
     def lookup(self, weight, kind, cin, cout, ci_real, co_real, s_co, s_ci, taps, flip):
         """(entry, fresh): the entry of this image of a registered live parameter (created on first request), and whether its
@@ -180,7 +182,7 @@ class PackPlan:
     def prepack(self, weights):
         """register `weights` (nn.Parameters) and bring every recorded image of THEIRS up to their current version in one
         launch (a table per set of weights: another live model's images are not this call's business); the amax arrays of
-        all of them in three launches (as prime_weight_amax)"""
+        all of them in one call of az_absmax_multi (as prime_weight_amax)"""
         with self.lock:
             self.purge()
             import weakref
@@ -199,7 +201,7 @@ class PackPlan:
             if not stale:
                 return
             with torch.no_grad(), torch.cuda.device(self.device):
-                # amax rows of the weights behind the stale images (persistent rows: slot 0 rewritten in place)
+                # amax rows of the weights behind the stale images (persistent rows: rewritten in place by az_absmax_multi)
                 ws = {}
                 for e in stale:
                     w = e.wref()
@@ -210,8 +212,7 @@ class PackPlan:
                     row = self.amax_row(w)
                     self.amax_rows[w.data_ptr()] = (row, self.registered[w.data_ptr()])
                     rows.append(row)
-                maxes = torch._foreach_norm([w.detach() for w in wl], float("inf"))
-                torch._foreach_copy_([r[0:1] for r in rows], [m.reshape(1) for m in maxes])
+                self.amax_op.run([w.detach() for w in wl], rows)
                 for w, row in zip(wl, rows):
                     amax.remember_weight_amax(w, row)
                 for e in stale:

@@ -227,6 +227,18 @@ int az_conv3d_wgrad(float *grad_w, float *workspace, long long workspace_bytes,
 #define AZ_AMAX_STRIDE 64
 #define AZ_AMAX_FLOATS (AZ_AMAX_SLOTS * AZ_AMAX_STRIDE)
 int az_absmax(float *amax, const float *x, long long n, void *stream);
+/* az_absmax of MANY tensors in one call, no launch per tensor (the weights of a model, once per optimizer step:
+ * activezero_amd/amax.py prime_weight_amax, packing.py PackPlan.prepack).  One descriptor per tensor: src (n > 0 floats, a
+ * float's alignment suffices) and amax, its amax array, zeroing included -- the arrays need not be adjacent.  The largest slot
+ * of each array holds the bits az_absmax gives for that tensor.  descs: nd descriptors in DEVICE memory; block_desc /
+ * first_block: as for az_pack_f16_multi below, one workgroup per 256 elements of one tensor, nblocks in all. */
+typedef struct AzAbsmaxDesc {
+    const float *src;
+    float *amax;
+    long long n;
+} AzAbsmaxDesc;
+int az_absmax_multi(const AzAbsmaxDesc *descs, const int *block_desc, const int *first_block, int nd, int nblocks,
+                    void *stream);
 /* Every f16x3 weight image of a model in ONE launch (round 5: a training step packed each weight twice -- forward image,
  * flipped / swapped input-gradient image -- with a launch each, ~175 per step).  One descriptor per image: `kind` names
  * the layout of the kernel that will read it (the per-tensor entry points az_conv2d_pack_weights_f16 /

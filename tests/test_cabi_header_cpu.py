@@ -17,7 +17,7 @@ from activezero_amd import _lib, overlap, packing
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODES = {ctypes.c_int: "i", ctypes.c_longlong: "q", ctypes.c_float: "f", ctypes.c_double: "d", ctypes.c_size_t: "z",
          ctypes.c_char_p: "s", ctypes.c_void_p: "p"}
-STRUCTS = {"AzPackDesc": _lib.PACK_DESC, "AzUnpackDesc": _lib.UNPACK_DESC}
+STRUCTS = {"AzPackDesc": _lib.PACK_DESC, "AzUnpackDesc": _lib.UNPACK_DESC, "AzAbsmaxDesc": _lib.ABSMAX_DESC}
 
 PROGRAM_HEAD = r"""
 #include <cstddef>
