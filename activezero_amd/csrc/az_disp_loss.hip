@@ -8,6 +8,7 @@
 // is the removed syncs and launches.
 #include "az_block_reduce.h"
 #include "az_common.h"
+#include "az_disp_terms.h"
 
 #define DL_BLOCK 256
 
@@ -58,7 +59,7 @@ disp_loss_bwd_kernel(float *__restrict__ g3, float *__restrict__ g2, float *__re
 }
 
 // acc: 0 sum|dd|  1 #(|dd|>1)  2 #(|dd|>2)  3 sum clip(|1000 dz|,0,100)  4 #(|dz|>2e-3)
-//      5 #(|dz|>4e-3)  6 #(|dz|>8e-3)  7 count      (dd = disparity error, dz = depth error in m)
+//      5 #(|dz|>4e-3)  6 #(|dz|>8e-3)  7 count      (dd = disparity error, dz = depth error in m; az_disp_terms.h)
 __global__ void __launch_bounds__(DL_BLOCK)
 disp_metrics_kernel(double *__restrict__ acc, const float *__restrict__ disp_gt,
                     const float *__restrict__ depth_gt, const float *__restrict__ disp_pred,
@@ -68,20 +69,16 @@ disp_metrics_kernel(double *__restrict__ acc, const float *__restrict__ disp_gt,
     for (long long i = (long long)blockIdx.x * DL_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * DL_BLOCK) {
         if (!mask[i]) continue;
         const float dp = disp_pred[i];
-        const float dd = fabsf(disp_gt[i] - dp);
-        // cascade_metrics.py:36-37: depth_pred = focal_length * baseline / disp_pred (metres)
-        const float zp = depth_pred ? depth_pred[i] : fb[i / per_batch] / dp;
-        const float zg = depth_gt[i];
-        const float dz = fabsf(zg - zp);
-        const float dmm = az_min_nan(az_max_nan(fabsf(zg * 1000.f - zp * 1000.f), 0.f), 100.f);  // torch.clip: NaN stays, inf -> 100
-        v[0] += dd;
-        v[1] += dd > 1.f ? 1.0 : 0.0;
-        v[2] += dd > 2.f ? 1.0 : 0.0;
-        v[3] += dmm;
-        v[4] += dz > 2e-3f ? 1.0 : 0.0;
-        v[5] += dz > 4e-3f ? 1.0 : 0.0;
-        v[6] += dz > 8e-3f ? 1.0 : 0.0;
-        v[7] += 1.0;
+        const float zp = depth_pred ? depth_pred[i] : az_dm_depth(fb[i / per_batch], dp);
+        const az_dm_px p = az_dm_pixel(disp_gt[i], depth_gt[i], dp, zp);  // az_disp_terms.h (shared with K22)
+        v[AZ_DM_EPE] += p.dd;
+        v[AZ_DM_BAD1] += p.bad1 ? 1.0 : 0.0;
+        v[AZ_DM_BAD2] += p.bad2 ? 1.0 : 0.0;
+        v[AZ_DM_MM] += p.dmm;
+        v[AZ_DM_Z2] += p.z2 ? 1.0 : 0.0;
+        v[AZ_DM_Z4] += p.z4 ? 1.0 : 0.0;
+        v[AZ_DM_Z8] += p.z8 ? 1.0 : 0.0;
+        v[AZ_DM_COUNT] += 1.0;
     }
     dl_flush<8>(v, acc);
 }

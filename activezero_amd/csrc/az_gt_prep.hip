@@ -149,3 +149,78 @@ extern "C" int az_gt_from_right(float *disp_l, float *extra_l, float *keep_s, ui
                        stats, disp_r, extra, keep, Ce, Ck, Hin, Win, H, W, scale_h, scale_w, lo, hi, rows);
     return az_launch_status();
 }
+
+// K23 -- the evaluation mask of a test instance in one launch: reference test.py:112-117, 162-193, the chain
+//     F.interpolate(robot_mask, mode="nearest").type(torch.int) == 0,  F.interpolate(realsense_depth, mode="nearest") > 0,
+//     (disp < max_disp) * (disp > 0) * ((depth > 0) & (depth < 1.25)) * robot * realsense  ->  .type(torch.bool)
+// One thread per output pixel: the auxiliary maps are read at gtp_src's indices in their OWN type (the loader delivers
+// float64; a float32 round trip could turn 0.99999999 into 1 before the truncating cast), no resized, integer or boolean
+// intermediate exists.  The count: popcount of a ballot per wave, LDS over the workgroup's waves, one atomic per
+// workgroup, issued only when non-zero.
+struct em_aux {  // an optional auxiliary map [B,h,w]
+    const void *p;
+    int f64, h, w;
+    float scale_h, scale_w;
+};
+
+template <class T>
+__device__ __forceinline__ T em_read(const em_aux &a, int b, int y, int x) {
+    const int ys = gtp_src(y, a.scale_h, a.h), xs = gtp_src(x, a.scale_w, a.w);
+    return static_cast<const T *>(a.p)[((size_t)b * a.h + ys) * a.w + xs];
+}
+
+__global__ void __launch_bounds__(256)
+eval_mask_kernel(uint8_t *__restrict__ mask, int *__restrict__ count, const float *__restrict__ disp_l,
+                 const float *__restrict__ depth_l, em_aux robot, em_aux rs, int H, int W, long long n, float max_disp,
+                 int exclude_bg, float depth_hi) {
+    __shared__ int wave_cnt[4];
+    int cnt = 0;
+    // (every lane of a wave makes the same trips: the ballot)
+    for (long long i0 = (long long)blockIdx.x * 256 + (threadIdx.x & ~63); i0 < n; i0 += (long long)gridDim.x * 256) {
+        const long long i = i0 + (threadIdx.x & 63);
+        bool on = false;
+        if (i < n) {
+            const float d = disp_l[i];
+            on = 0.f < d && d < max_disp;
+            if (exclude_bg) {
+                const float z = depth_l[i];
+                on = on && 0.f < z && z < depth_hi;
+            }
+            const long long row = i / W;
+            const int x = (int)(i - row * W), b = (int)(row / H), y = (int)(row - (long long)b * H);
+            if (robot.p != nullptr)  // (int) truncates toward zero, as .type(torch.int) does
+                on = on && (robot.f64 ? (int)em_read<double>(robot, b, y, x) : (int)em_read<float>(robot, b, y, x)) == 0;
+            if (rs.p != nullptr) on = on && (rs.f64 ? em_read<double>(rs, b, y, x) > 0.0 : em_read<float>(rs, b, y, x) > 0.f);
+            mask[i] = on ? 1 : 0;
+        }
+        cnt += __popcll(__ballot(on));  // wave-uniform
+    }
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int c = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        if (c != 0) atomicAdd(count, c);
+    }
+}
+
+static bool em_aux_ok(const void *p, int f64, int h, int w) {
+    return (f64 == 0 || f64 == 1) && (p == nullptr || (h > 0 && w > 0));
+}
+
+extern "C" int az_eval_mask(uint8_t *mask, int32_t *count, const float *disp_l, const float *depth_l, const void *robot,
+                            int robot_f64, int Hr, int Wr, const void *realsense, int realsense_f64, int Hs, int Ws, int B,
+                            int H, int W, float max_disp, int exclude_bg, float depth_hi, void *stream) {
+    AZ_REQUIRE_PTR(mask); AZ_REQUIRE_PTR(count); AZ_REQUIRE_PTR(disp_l);
+    if (exclude_bg) AZ_REQUIRE_PTR(depth_l);
+    AZ_REQUIRE(B > 0 && H > 0 && W > 0);
+    AZ_REQUIRE(em_aux_ok(robot, robot_f64, Hr, Wr) && em_aux_ok(realsense, realsense_f64, Hs, Ws));
+    // ATen's scale when a size is given: (float)in / out
+    const em_aux a_robot = {robot, robot_f64, Hr, Wr, (float)Hr / (float)H, (float)Wr / (float)W};
+    const em_aux a_rs = {realsense, realsense_f64, Hs, Ws, (float)Hs / (float)H, (float)Ws / (float)W};
+    const long long n = (long long)B * H * W;
+    hipStream_t s = az_stream(stream);
+    if (hipMemsetAsync(count, 0, sizeof(int32_t), s) != hipSuccess) return AZ_ELAUNCH;  // (the zeroing is included)
+    hipLaunchKernelGGL(eval_mask_kernel, dim3(az_grid_for(n, 256)), dim3(256), 0, s, mask, count, disp_l, depth_l, a_robot,
+                       a_rs, H, W, n, max_disp, exclude_bg, depth_hi);
+    return az_launch_status();
+}

@@ -320,6 +320,111 @@ def disp_metrics(disp_gt, depth_gt, disp_pred, mask, focal_x_baseline=None, dept
 
 
 # ----------------------------------------------------------------------------
+# K22 metrics per image and object label, K23 the evaluation mask (test.py around the network)
+# ----------------------------------------------------------------------------
+MAX_LABELS = _lib.CONST["AZ_OBJ_MAX_LABELS"]
+
+
+def _obj_metrics(disp_gt, depth_gt, disp_pred, mask, label, num_labels, focal_x_baseline, depth_pred):
+    """the launch of obj_metrics -> (the fp64 buffer that holds its three outputs, B, L)"""
+    dg = _chk(disp_gt.contiguous(), "disp_gt")
+    zg = _chk(depth_gt.contiguous(), "depth_gt")
+    dp = _chk(disp_pred.contiguous(), "disp_pred")
+    if not (dg.shape == zg.shape == dp.shape):
+        raise RuntimeError("disp_gt, depth_gt and disp_pred must have identical shapes")
+    m = _mask_u8(mask, dg)
+    if m is None:
+        raise RuntimeError("mask is required")
+    nl = int(num_labels)
+    if not 1 <= nl <= MAX_LABELS:
+        raise RuntimeError(f"num_labels must be in [1, {MAX_LABELS}], got {num_labels}")
+    lb = None
+    if label is not None:
+        lb = _chk(label.contiguous(), "label", torch.int32)
+        if lb.numel() != dg.numel() or lb.shape[0] != dg.shape[0]:
+            raise RuntimeError(f"label: shape {tuple(lb.shape)} does not match {tuple(dg.shape)}")
+    b = dg.shape[0]
+    zp = _chk(depth_pred.contiguous(), "depth_pred") if depth_pred is not None else None
+    fb = None
+    if zp is None:
+        if focal_x_baseline is None:
+            raise RuntimeError("focal_x_baseline or depth_pred is required")
+        fb = _chk(focal_x_baseline.contiguous().reshape(-1), "focal_x_baseline")
+        if fb.numel() != b:
+            raise RuntimeError("focal_x_baseline must hold one value per batch element")
+    elif zp.shape != dg.shape:
+        raise RuntimeError("depth_pred must have the shape of disp_pred")
+    buf = torch.zeros(_obj_words(b, nl), dtype=torch.float64, device=dg.device)  # the three outputs: one zeroing, one copy
+    acc, present, stats = _obj_views(buf, b, nl)
+    with torch.cuda.device(dg.device):
+        _call("az_obj_metrics", _p(acc), _p(present), _p(stats), _p(dg), _p(zg), _p(dp), _p(zp), _p(fb), _p(m), _p(lb),
+              b, nl, dg.numel() // max(b, 1), _stream())
+    return buf, b, nl
+
+
+def obj_metrics(disp_gt, depth_gt, disp_pred, mask, label=None, num_labels=1, focal_x_baseline=None, depth_pred=None):
+    """The eight sums of disp_metrics per image and per object label, in one launch: maps [B,1,H,W] (or any shape whose
+    first axis is the batch), mask bool / uint8, label int32 of the same shape or None (every pixel has label 0).
+    Returns (acc [B,L,8] float64, present [B,L] int32 -- pixels of image b with label l, masked or not --, stats [1] int32
+    -- pixels whose label is outside [0, L)), L = num_labels <= MAX_LABELS, all on the device.  No host sync."""
+    return _obj_views(*_obj_metrics(disp_gt, depth_gt, disp_pred, mask, label, num_labels, focal_x_baseline, depth_pred))
+
+
+def obj_metrics_host(disp_gt, depth_gt, disp_pred, mask, label=None, num_labels=1, focal_x_baseline=None, depth_pred=None):
+    """obj_metrics, its three results as numpy arrays: the launch and then ONE device->host copy (the only sync)."""
+    buf, b, nl = _obj_metrics(disp_gt, depth_gt, disp_pred, mask, label, num_labels, focal_x_baseline, depth_pred)
+    return _obj_views(buf.cpu().numpy(), b, nl)
+
+
+def _obj_words(b, nl):
+    """fp64 words of the buffer obj_metrics keeps its three outputs in: acc, then present and stats as int32 pairs"""
+    return b * nl * 8 + (b * nl + 2) // 2
+
+
+def _obj_views(buf, b, nl):
+    """(acc [b,nl,8] float64, present [b,nl] int32, stats [1] int32) as views of that buffer -- a tensor or a numpy array"""
+    i32 = torch.int32 if isinstance(buf, torch.Tensor) else "int32"
+    ints = buf[b * nl * 8:].view(i32)
+    return buf[:b * nl * 8].reshape(b, nl, 8), ints[:b * nl].reshape(b, nl), ints[b * nl:b * nl + 1]
+
+
+def _aux_map(t, name, b, device):
+    """an optional [B,h,w] / [B,1,h,w] map of float32 or float64 -> (tensor, is_f64, h, w)"""
+    if t is None:
+        return None, 0, 0, 0
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"{name}: expected a float32 or float64 tensor")
+    t = _chk(t.contiguous(), name, t.dtype)
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or t.shape[0] != b or t.device != device or t.numel() == 0:
+        raise RuntimeError(f"{name}: shape {tuple(t.shape)}: expected [{b},h,w] or [{b},1,h,w] on {device}")
+    return t, int(t.dtype == torch.float64), t.shape[1], t.shape[2]
+
+
+def eval_mask(disp_l, depth_l, max_disp, exclude_bg=True, robot_mask=None, realsense_depth=None, depth_hi=1.25):
+    """test.py:112-117, 162-193 in one launch: disp_l, depth_l [B,1,H,W] float32; robot_mask / realsense_depth optional maps
+    [B,h,w] or [B,1,h,w] of their own size, float32 or float64, read at the nearest-resize indices in their own type.
+    mask = (0 < disp_l < max_disp) & (0 < depth_l < depth_hi if exclude_bg) & ((int)robot == 0) & (realsense > 0).
+    Returns (mask [B,1,H,W], a bool view of the byte tensor the kernel wrote, count int32 [1] on the device).  No host sync."""
+    d = _chk(disp_l, "disp_l")
+    z = _chk(depth_l, "depth_l")
+    if d.dim() != 4 or d.shape[1] != 1 or z.shape != d.shape or z.device != d.device:
+        raise RuntimeError("disp_l and depth_l must be [B,1,H,W] of one shape")
+    b, _, h, w = d.shape
+    if d.numel() == 0:
+        raise RuntimeError("disp_l is empty")
+    robot, r64, hr, wr = _aux_map(robot_mask, "robot_mask", b, d.device)
+    rs, s64, hs, ws = _aux_map(realsense_depth, "realsense_depth", b, d.device)
+    mask = torch.empty(b, 1, h, w, dtype=torch.uint8, device=d.device)
+    count = torch.empty(1, dtype=torch.int32, device=d.device)
+    with torch.cuda.device(d.device):
+        _call("az_eval_mask", _p(mask), _p(count), _p(d), _p(z), _p(robot), r64, hr, wr, _p(rs), s64, hs, ws, b, h, w,
+              float(max_disp), 1 if exclude_bg else 0, float(depth_hi), _stream())
+    return mask.view(torch.bool), count
+
+
+# ----------------------------------------------------------------------------
 # K18 ground truth from the right view, K19 error colour images
 # ----------------------------------------------------------------------------
 def gt_from_right(disp_r, extra=None, keep=None, *, scale_factor=0.5, size=None, lo=0.0, hi=float("inf"), check=False):

@@ -9,8 +9,8 @@ An addition, not a shadow of a reference module.  Opt in inside train_sample (tr
     from utils.gt_prep import prepare_sim_gt
     disp_gt_l, depth_gt, mask = prepare_sim_gt(sample, cfg.MODEL.MAX_DISP)
 
-in place of train.py:248-249, 255-272, and in test.py with `prepare_test_gt(data)` in place of :82-85, 91-110
-(INTEGRATION.md).
+in place of train.py:248-249, 255-272, and in test.py with `prepare_test_gt(data)` in place of :82-85, 91-110 and
+`prepare_test_mask(...)` (the fused K23 kernel, az_eval_mask) in place of the mask lines :112-117, 162-193.
 """
 import torch
 
@@ -51,3 +51,15 @@ def prepare_test_gt(sample_or_tensors, size=(540, 960), device=None, check=False
         label = label.to(torch.float32)
     img_disp_l, img_depth_l, label_s, _, _ = ops.gt_from_right(disp_r, extra=depth_r, keep=label, size=size, check=check)
     return img_disp_l, img_depth_l, label_s.type(torch.int)
+
+
+def prepare_test_mask(img_disp_l, img_depth_l, max_disp, exclude_bg=True, robot_mask=None, realsense_depth=None, depth_hi=1.25):
+    """test.py:112-117, 162-193: the evaluation mask [B,1,H,W] bool of
+        (img_disp_l < max_disp) * (img_disp_l > 0) * ((img_depth_l > 0) & (img_depth_l < 1.25))   (the last if exclude_bg)
+        * (F.interpolate(robot_mask, (H, W), mode="nearest").type(torch.int) == 0)                 (LOSSES.ONREAL)
+        * (F.interpolate(realsense_depth, (H, W), mode="nearest") > 0)                             (LOSSES.EXCLUDE_ZEROS)
+    in ONE launch of the fused K23 kernel (az_eval_mask): robot_mask / realsense_depth are the loader's maps, [B,h,w] or
+    [B,1,h,w] at their own size, float32 or float64, read in place in their own type; None leaves the term out.  Nothing
+    synchronises."""
+    mask, _ = ops.eval_mask(img_disp_l, img_depth_l, max_disp, exclude_bg, robot_mask, realsense_depth, depth_hi)
+    return mask

@@ -619,6 +619,22 @@ int az_gt_from_right(float *disp_l, float *extra_l, float *keep_s, uint8_t *mask
                      const float *extra, const float *keep, int N, int Ce, int Ck, int Hin, int Win, int H, int W,
                      float scale_h, float scale_w, float lo, float hi, void *stream);
 
+/* ---- K23: the evaluation mask of a test instance (az_gt_prep.hip) ---------------------------------------------
+ * replaces test.py:112-117, 162-193: two F.interpolate(mode="nearest"), a .type(torch.int), five compares and four products.
+ * disp_l, depth_l [B,1,H,W] f32 (depth_l may be NULL when exclude_bg is 0); robot [B,Hr,Wr] and realsense [B,Hs,Ws]: each
+ * NULL (the term is left out) or a map read in its OWN type -- *_f64 0 = float32, 1 = float64 -- and never converted.
+ *   mask[b,y,x] = 0 < disp_l < max_disp
+ *                 && (!exclude_bg || 0 < depth_l < depth_hi)
+ *                 && (robot == NULL || (int)robot[b, ys, xs] == 0)        (int): truncation toward zero
+ *                 && (realsense == NULL || realsense[b, ys', xs'] > 0)
+ * with (ys, xs) ATen's legacy "nearest" source index from the map's own size to (H, W), as in K18, scale = (float)in / out;
+ * both directions (an auxiliary map may be smaller than the output).  mask: one byte per pixel, fully written; count[0]: the
+ * number of set pixels -- zeroed by the call itself, on the stream, then one atomic per workgroup.
+ * A required pointer null: AZ_ENULL; a non-positive size, a *_f64 that is not 0 or 1: AZ_EINVAL. */
+int az_eval_mask(uint8_t *mask, int32_t *count, const float *disp_l, const float *depth_l, const void *robot,
+                 int robot_f64, int Hr, int Wr, const void *realsense, int realsense_f64, int Hs, int Ws, int B, int H,
+                 int W, float max_disp, int exclude_bg, float depth_hi, void *stream);
+
 /* ---- K19: colour-coded error images (az_error_img.hip) ---------------------------------------------------
  * replaces utils/util.py:185-244 depth_error_img / disp_error_img with their tables gen_error_colormap_depth / _disp
  * (:143-182), called on the host by train.py:353-356 and test.py:244,260 -- for all B images, on the device.
@@ -735,6 +751,24 @@ int az_disp_loss_bwd(float *g3, float *g2, float *g1, const float *pred3, const 
 int az_disp_metrics(double *acc8, const float *disp_gt, const float *depth_gt,
                     const float *disp_pred, const float *depth_pred, const float *focal_x_baseline,
                     const unsigned char *mask, int B, long long per_batch, void *stream);
+
+/* ---- K22: the metrics of a test batch per image and per object label, one pass (az_obj_metrics.hip) ------------
+ * replaces utils/cascade_metrics.py:65-126 compute_obj_err -- label.unique().tolist() (a host sync), then per object a
+ * (label == obj) & mask temporary and a chain of masked reductions over the whole map -- and gives compute_err_metric per
+ * image of a batch.  Maps [B,1,H,W] f32 of per_image = H W pixels each; mask one byte per pixel; label int32 per pixel or
+ * NULL = every pixel has label 0; depth_pred NULL -> focal_x_baseline[b] / disp_pred, as in az_disp_metrics.  1 <= L <=
+ * AZ_OBJ_MAX_LABELS.  All three outputs are CALLER-ZEROED and added to:
+ *   acc[B][L][8]   f64: the eight sums of az_disp_metrics (same slots, same float32 terms) over the pixels of image b with
+ *                  mask != 0 && label == l; counts exact, the order of the two sums unspecified
+ *   present[B][L]  int32: the pixels of image b with label == l, masked or not (the reference lists its objects by
+ *                  label.unique() over all pixels)
+ *   stats[1]       int32: the pixels whose label is outside [0, L); they contribute nothing else
+ * A required pointer null: AZ_ENULL; B < 0, per_image < 0, L < 1: AZ_EINVAL; L > AZ_OBJ_MAX_LABELS or per_image >= 2^31:
+ * AZ_EUNSUPPORTED -- all before any launch.  No allocation, no synchronisation. */
+#define AZ_OBJ_MAX_LABELS 64
+int az_obj_metrics(double *acc, int32_t *present, int32_t *stats, const float *disp_gt, const float *depth_gt,
+                   const float *disp_pred, const float *depth_pred, const float *focal_x_baseline, const uint8_t *mask,
+                   const int32_t *label, int B, int L, long long per_image, void *stream);
 
 /* ---- K15: RAFT-Stereo convex upsampling (az_convex_up.hip) -------------------------------------
  * Replaces nets/raft/raft_stereo.py:74-86 `RAFTStereo.upsample_flow` (softmax over the 9 taps of a materialised

@@ -505,6 +505,186 @@ def error_img(out_path=None):
     _write_case(rec, out_path)
 
 
+def eval_epilogue(out_path=None):
+    """K22 against the per-object loop it replaces and K23 against its torch chain, at B = 1 and B = 4, 540x960, 17 objects
+    laid out as blobs; equality first, then host wall time and kernel time; launches and syncs counted from the code"""
+    import json
+    import statistics
+    import time
+    import numpy as np
+    import torch.nn.functional as F
+    import bench as _bench
+    from activezero_amd import ops
+    from activezero_amd.utils import cascade_metrics as cm
+    dev = torch.device("cuda:0")
+    H, W, L, reps, MAX_DISP = 540, 960, 17, 20, 192
+    probe = _bench.hbm_probe(dev)["GB/s"]
+    doc = {"case": "eval_epilogue", "copy_probe_GB/s": probe,
+           "timing": "host wall time per call on rotated input sets, device drained before and after, median of %d; kernel time "
+                     "by events around one pass over the sets (together larger than the 256 MiB cache)" % reps}
+
+    def wall(fn, sets):
+        for i in range(min(sets, 4)):
+            fn(i)
+        us = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(sets):
+                fn(i)
+            torch.cuda.synchronize()
+            us.append((time.perf_counter() - t0) / sets * 1e6)
+        return {"us_per_call": statistics.median(us), "min_us": min(us)}
+
+    def kernel_ms(launch, sets):
+        for _ in range(2):
+            for i in range(sets):
+                launch(i)
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(sets):
+                launch(i)
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / sets)
+        return statistics.median(ms), min(ms)
+
+    for B in (1, 4):
+        sets = 32 if B == 1 else 8
+        g = torch.Generator(device=dev).manual_seed(B)
+        yy, xx = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
+        data = []
+        for s in range(sets):
+            # 17 objects as blobs of 135 x 160 pixels, shifted per set and image
+            label = torch.stack([(((yy + 7 * (s + b)) // 135) * 6 + (xx + 11 * b) // 160) % L for b in range(B)])[:, None].to(torch.int32)
+            disp_gt = (8 + 112 * torch.rand(B, 1, H, W, device=dev, generator=g)).contiguous()
+            disp_pred = disp_gt + 3 * torch.randn(B, 1, H, W, device=dev, generator=g)
+            focal = torch.full((B, 1, 1, 1), 446.31, device=dev)
+            base = torch.full((B, 1, 1, 1), 0.055, device=dev)
+            depth_gt = (focal * base / disp_gt).contiguous()
+            mask = torch.rand(B, 1, H, W, device=dev, generator=g) > 0.2
+            data.append((disp_gt, depth_gt, disp_pred.clamp_min(0.5).contiguous(), focal, base, label.contiguous(), mask))
+
+        def chain(i):
+            """utils/cascade_metrics.py:65-126 as torch operators, one image or the batch as one set"""
+            disp_gt, depth_gt, disp_pred, focal, base, label, mask = data[i]
+            depth_pred = focal * base / disp_pred
+            out = np.zeros((4, L))
+            for obj in label.unique():
+                k = int(obj.item())
+                own = label == k
+                out[0, k] += F.l1_loss(disp_gt[own * mask], disp_pred[own * mask], reduction="mean").item()
+                mm = torch.clip(torch.abs(depth_gt[own * mask] * 1000 - depth_pred[own * mask] * 1000), min=0, max=100)
+                out[1, k] += torch.mean(mm).item()
+                dz = torch.abs(depth_gt[own * mask] - depth_pred[own * mask])
+                out[2, k] += dz[dz > 4e-3].numel() / dz.numel()
+                out[3, k] += 1
+            return out
+
+        def k12_loop(i):
+            """compute_obj_err as it ran before K22: one az_disp_metrics launch per object, one copy"""
+            disp_gt, depth_gt, disp_pred, focal, base, label, mask = data[i]
+            depth_pred = (focal * base / disp_pred).contiguous()
+            accs = [ops.disp_metrics(disp_gt, depth_gt, disp_pred, (label == obj) & mask, None, depth_pred)
+                    for obj in label.unique().tolist()]
+            return torch.stack(accs).tolist()
+
+        def fused(i):
+            return cm.compute_obj_err(*data[i])
+
+        got, want = fused(0), chain(0)
+        assert np.array_equal(got[3], want[3]), "object counts differ"
+        for k in (0, 1):  # float32 means of the chain against fp64 sums
+            np.testing.assert_allclose(got[k], want[k], rtol=2e-5)
+        # a ratio of counts: equal when torch's float32 division rounds as the kernel's does (recorded), else a pixel or two apart
+        np.testing.assert_allclose(got[2], want[2], atol=1e-4)
+        per = cm.compute_obj_err_per_image(*data[0])
+        single = [cm.compute_obj_err(*(t[b:b + 1] for t in data[0])) for b in range(B)]
+        for k in range(4):
+            np.testing.assert_allclose(per[k], sum(s[k] for s in single), rtol=1e-12)
+        objs = int(want[3].sum())
+        rec = {"maps": [B, 1, H, W], "objects_present": objs, "depth_err4_equal_to_the_chain": bool(np.array_equal(got[2], want[2])),
+               "k22_compute_obj_err": dict(wall(fused, sets), library_launches=1, host_syncs=1, launches_are=(
+                   "az_obj_metrics; beside it the focal * baseline product and the zero fill of the 4.4 KB output buffer, then the one copy")),
+               "per_object_operator_chain": dict(wall(chain, sets), launches_at_least=4 + 33 * objs, host_syncs=1 + 10 * objs, launches_are=(
+                   "unique (a sort, a sync) and the depth division, then per object: item, the compare, 6 products, 6 boolean-index "
+                   "compactions (nonzero with a sync, gather), 14 element-wise and reduction operators, 3 item(); counted from the code")),
+               "per_object_k12_loop": dict(wall(k12_loop, sets), launches=3 + 4 * objs, host_syncs=2, launches_are=(
+                   "unique + tolist (a sync), the depth division, per object a compare, an and, a zero fill and az_disp_metrics, "
+                   "then stack and one copy"))}
+        rec["speedup_vs_operator_chain"] = rec["per_object_operator_chain"]["us_per_call"] / rec["k22_compute_obj_err"]["us_per_call"]
+        rec["speedup_vs_k12_loop"] = rec["per_object_k12_loop"]["us_per_call"] / rec["k22_compute_obj_err"]["us_per_call"]
+
+        # the kernels alone on preallocated outputs
+        fb = [(d[3] * d[4]).reshape(-1).contiguous() for d in data]
+        m8 = [d[6].view(torch.uint8) for d in data]
+        buf = torch.zeros(ops._obj_words(B, L), dtype=torch.float64, device=dev)
+        acc, present, stats = ops._obj_views(buf, B, L)
+        acc8 = torch.zeros(8, dtype=torch.float64, device=dev)
+        P = H * W
+
+        def k22(i, lab=True, nl=L):
+            d = data[i]
+            ops._call("az_obj_metrics", acc.data_ptr(), present.data_ptr(), stats.data_ptr(), d[0].data_ptr(), d[1].data_ptr(),
+                      d[2].data_ptr(), None, fb[i].data_ptr(), m8[i].data_ptr(), d[5].data_ptr() if lab else None, B, nl, P, ops._stream())
+
+        def k12(i):
+            d = data[i]
+            ops._call("az_disp_metrics", acc8.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), None, fb[i].data_ptr(),
+                      m8[i].data_ptr(), B, P, ops._stream())
+
+        for name, launch, per_px in (("k22_17_labels", k22, 17 + 4), ("k22_no_label", lambda i: k22(i, False, 1), 17), ("k12_whole_batch", k12, 17)):
+            m, lo = kernel_ms(launch, sets)
+            nbytes = float(per_px) * B * P
+            rec[name] = {"ms": m, "min_ms": lo, "MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6, "of_copy_probe": nbytes / m / 1e6 / probe,
+                         "copy_probe_ms_for_these_bytes": nbytes / probe / 1e6}
+
+        # K23: the loader's robot mask and RealSense depth at 1080 x 1920, float64
+        aux = [((torch.rand(B, 1080, 1920, device=dev, generator=g, dtype=torch.float64) > 0.8).double(),
+                torch.rand(B, 1080, 1920, device=dev, generator=g, dtype=torch.float64).clamp_min(0.25) - 0.25) for _ in range(sets)]
+
+        def mask_chain(i):
+            """test.py:112-117, 162-193"""
+            disp, depth = data[i][0], data[i][1]
+            robot = F.interpolate(aux[i][0].unsqueeze(1), (H, W), mode="nearest", recompute_scale_factor=False).type(torch.int) == 0
+            ground = (depth > 0) & (depth < 1.25)
+            m = (disp < MAX_DISP) * (disp > 0) * ground * robot
+            rs = F.interpolate(aux[i][1].unsqueeze(1), (H, W), mode="nearest", recompute_scale_factor=False)
+            return (m * (rs > 0)).type(torch.bool)
+
+        def mask_fused(i):
+            return ops.eval_mask(data[i][0], data[i][1], MAX_DISP, True, aux[i][0], aux[i][1])[0]
+
+        assert torch.equal(mask_fused(0), mask_chain(0))
+        rec["k23_eval_mask"] = dict(wall(mask_fused, sets), launches=2, host_syncs=0, launches_are="the memset of the counter, the kernel")
+        rec["mask_operator_chain"] = dict(wall(mask_chain, sets), launches=14, host_syncs=0, launches_are=(
+            "2 nearest resizes, the int cast, 6 compares, the and, 4 products; counted from the code"))
+        rec["k23_speedup"] = rec["mask_operator_chain"]["us_per_call"] / rec["k23_eval_mask"]["us_per_call"]
+        out_m = torch.empty(B, 1, H, W, dtype=torch.uint8, device=dev)
+        cnt = torch.empty(1, dtype=torch.int32, device=dev)
+
+        def k23(i):
+            ops._call("az_eval_mask", out_m.data_ptr(), cnt.data_ptr(), data[i][0].data_ptr(), data[i][1].data_ptr(), aux[i][0].data_ptr(),
+                      1, 1080, 1920, aux[i][1].data_ptr(), 1, 1080, 1920, B, H, W, float(MAX_DISP), 1, 1.25, ops._stream())
+
+        m, lo = kernel_ms(k23, sets)
+        # 4 + 4 read and 1 written per pixel, and of each float64 map every second element of every second row: whole 64-byte
+        # lines of the 540 selected rows
+        nbytes = float(B) * P * 9 + 2 * float(B) * H * 1920 * 8
+        rec["k23_kernel"] = {"ms": m, "min_ms": lo, "touched_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6, "of_copy_probe": nbytes / m / 1e6 / probe,
+                             "copy_probe_ms_for_these_bytes": nbytes / probe / 1e6, "includes": "the 4-byte memset of the counter"}
+        doc["B%d" % B] = rec
+        del data, aux
+    print(json.dumps(doc))
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(doc, indent=1) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "eval_epilogue":
+    eval_epilogue(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] in ("gt_prep", "error_img"):
     {"gt_prep": gt_prep, "error_img": error_img}[sys.argv[1]](sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
