@@ -60,7 +60,9 @@ class _BNAct(torch.autograd.Function):
                 scale, shift = eval_affine(bn, xr, cache=cache)
                 _call("az_bn3d_apply", _p(yr), _p(xr), _p(scale), _p(shift), _p(rr), int(relu), nvox * groups, c,
                       None, _stream())
-                ctx.save_for_backward(xr, yr if relu else None, gamma, scale, bn.running_mean.clone())
+                # (1/sqrt(running_var + eps) from the statistics themselves: d gamma does not depend on gamma)
+                ctx.save_for_backward(xr, yr if relu else None, scale, bn.running_mean.clone(),
+                                      (bn.running_var + eps).rsqrt())
                 ctx.cfg = (False, relu, residual is not None, groups, (n, c, h, w))
                 return yr.permute(0, 3, 1, 2)
             ws_bytes = lib.az_bn2d_workspace(groups, nvox, c)
@@ -94,10 +96,8 @@ class _BNAct(torch.autograd.Function):
         if not training:
             # frozen statistics (fine-tuning in eval mode): y = relu?(x*s + t + res), s = gamma*rinv,
             # t = beta - running_mean*s.  A rarely used path: plain tensor ops.
-            xr, yr, gamma, scale, rm = ctx.saved_tensors
+            xr, yr, scale, rm, rinv = ctx.saved_tensors
             dz = gr * (yr > 0).to(gr.dtype) if relu else gr
-            g_ = gamma.detach()
-            rinv = torch.where(g_ != 0, scale / g_, torch.zeros_like(scale))
             dgamma = (dz * (xr - rm)).sum(dim=(0, 1, 2)) * rinv
             dbeta = dz.sum(dim=(0, 1, 2))
             g_res = dz.permute(0, 3, 1, 2) if has_res else None

@@ -473,8 +473,9 @@ class _ConvBN(torch.autograd.Function):
                 _call("az_bn3d_apply", _p(y), _p(raw), _p(scale), _p(shift), _p(residual), int(relu),
                       raw.numel() // cout, cout, _p(y_amax), _stream())
                 _set_amax(y, y_amax)
+                # (1/sqrt(running_var + eps) from the statistics themselves: d gamma does not depend on gamma)
                 ctx.save_for_backward(x, weight, gamma, raw, y if relu else None, bn.running_mean.clone(),
-                                      scale, None, None)
+                                      scale, (bn.running_var + eps).rsqrt(), None)
                 ctx.cfg = (mode, relu, residual is not None, cin, cout, arith, False)
                 return y
             raw, part, cnt, ntiles = _conv(x, weight, mode, arith.conv, stats=True)
@@ -527,10 +528,10 @@ class _ConvBN(torch.autograd.Function):
                 # y = relu?(raw * s + t + res) with s = gamma * rinv, t = beta - running_mean * s (constants
                 # of the running statistics): dz = gy * [y > 0]; d raw = dz * s; d gamma = sum dz (raw - rm) rinv;
                 # d beta = sum dz.  A rarely used path (frozen-BN fine-tuning): plain tensor ops.
-                s_, rm = invstd, mean  # saved slots: (running_mean copy, scale)
+                # (the eval-mode forward saved running_mean's copy, the scale and 1/sqrt(running_var + eps) in these slots)
+                rm, s_, rinv = mean, invstd, scale
                 dz = gy * (y > 0).to(gy.dtype) if relu else gy
                 dbeta = dz.sum(dim=(0, 1, 2, 3))
-                rinv = torch.where(gamma.detach() != 0, s_ / gamma.detach(), torch.zeros_like(s_))
                 dgamma = (dz * (raw - rm)).sum(dim=(0, 1, 2, 3)) * rinv
                 dx_raw = (dz * s_).contiguous()
                 g_res = dz if has_res else None
