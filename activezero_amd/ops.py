@@ -497,6 +497,53 @@ def error_img(est, gt, mask, kind="disp", abs_thres=None, rel_thres=0.05, channe
 
 
 # ----------------------------------------------------------------------------
+# K24 the six result images of a test batch as RGBA bytes
+# ----------------------------------------------------------------------------
+RESULT_PANELS = ("pred_disp", "gt_disp", "pred_disp_abs_err_cmap", "pred_depth", "gt_depth", "pred_depth_abs_err_cmap")
+
+
+def result_images(pred_disp, gt_disp, gt_depth, mask, focal_x_baseline, max_disp, depth_hi=1.25, disp_abs_thres=3.0,
+                  disp_rel_thres=0.05, depth_scale=1000.0, depth_abs_thres=1.0, return_flags=False):
+    """test.py:235-260 with utils/test_util.py:59-107 save_img for every image of a batch, on the device: the bytes plt.imsave
+    writes for pred_disp, gt_disp, the disparity error image, pred_depth = focal_x_baseline / pred_disp, gt_depth and the depth
+    error image (RESULT_PANELS, save_img's order) -> uint8 [B,6,H,W,4] RGBA.  pred_disp: any [B,1,H,W] float32 view whose last
+    stride is 1 (the crop of a padded prediction, test.py:208, is not copied); gt_disp, gt_depth contiguous [B,1,H,W]; mask
+    bool or uint8; focal_x_baseline one float32 per image.  return_flags: also the int32 [B] word of az_result_images (bit m:
+    panel m of the image has a masked pixel).  No host sync."""
+    if not isinstance(pred_disp, torch.Tensor) or pred_disp.dim() != 4 or pred_disp.shape[1] != 1:
+        raise RuntimeError("pred_disp must be a [B,1,H,W] tensor")
+    b, _, h, w = pred_disp.shape
+    if pred_disp.numel() == 0:
+        raise RuntimeError("pred_disp is empty")
+    if w > 1 and pred_disp.stride(3) != 1:
+        raise RuntimeError("pred_disp: the last dimension must have stride 1")
+    if pred_disp.device.type != "cuda":
+        raise RuntimeError(f"pred_disp: must live on the GPU (got {pred_disp.device}); the HIP path has no CPU fallback")
+    if pred_disp.dtype != torch.float32:
+        raise RuntimeError(f"pred_disp: expected torch.float32, got {pred_disp.dtype}")
+    # a dimension of size 1 has no stride to speak of: give it the contiguous one
+    row_stride = pred_disp.stride(2) if h > 1 else w
+    img_stride = pred_disp.stride(0) if b > 1 else h * row_stride
+    gd = _chk(gt_disp, "gt_disp")
+    gz = _chk(gt_depth, "gt_depth")
+    if gd.shape != pred_disp.shape or gz.shape != pred_disp.shape or gd.device != pred_disp.device or gz.device != gd.device:
+        raise RuntimeError("pred_disp, gt_disp and gt_depth must be [B,1,H,W] of one shape on one device")
+    if mask is None:
+        raise RuntimeError("mask is required")
+    m = _mask_u8(mask, gd)
+    fb = _chk(focal_x_baseline.contiguous().reshape(-1), "focal_x_baseline")
+    if fb.numel() != b:
+        raise RuntimeError("focal_x_baseline must hold one value per batch element")
+    out = torch.empty(b, 6, h, w, 4, dtype=torch.uint8, device=gd.device)
+    flags = torch.empty(b, dtype=torch.int32, device=gd.device)
+    with torch.cuda.device(gd.device):
+        _call("az_result_images", _p(out), _p(flags), _p(pred_disp), row_stride, img_stride, _p(gd), _p(gz), _p(m), _p(fb),
+              float(max_disp), float(depth_hi), float(disp_abs_thres), float(disp_rel_thres), float(depth_scale),
+              float(depth_abs_thres), b, h, w, _stream())
+    return (out, flags) if return_flags else out
+
+
+# ----------------------------------------------------------------------------
 # K15 RAFT-Stereo convex upsampling
 # ----------------------------------------------------------------------------
 def _chk_mask(mask, name="mask"):

@@ -648,6 +648,38 @@ int az_eval_mask(uint8_t *mask, int32_t *count, const float *disp_l, const float
 int az_error_img(float *out, const float *est, const float *gt, const uint8_t *mask, int kind, float abs_thres,
                  float rel_thres, int layout, int B, int H, int W, void *stream);
 
+/* ---- K24: the six result images of a test batch as RGBA bytes (az_result_img.hip) ---------------------------------
+ * replaces test.py:208-209, 235-260 with utils/test_util.py:59-107 save_img (four float maps copied to the host, [ground_mask]
+ * = -1, np.ma.masked_where(x == -1, x), matplotlib's Normalize and viridis table inside plt.imsave) and the two error images
+ * of utils/util.py:143-244 sent through the same call -- for all B images, on the device, bit for bit the bytes plt.imsave
+ * (matplotlib 3.10) writes.  pred_disp is read through its strides in floats: element (b,y,x) at b pred_img_stride + y
+ * pred_row_stride + x, so the crop of the padded prediction (test.py:208) is a pointer offset; gt_disp, gt_depth [B,1,H,W] f32
+ * contiguous; mask one byte per pixel; focal_x_baseline [B] f32, the product made by the caller as for K22.
+ * out [B][6][H][W][4] R, G, B, A bytes, 4-byte aligned, fully written; panels in save_img's order: 0 pred_disp, 1 gt_disp,
+ * 2 pred_disp_abs_err_cmap, 3 pred_depth, 4 gt_depth, 5 pred_depth_abs_err_cmap.
+ *   viridis   panels 0, 1, 3, 4: x = pred_disp, gt_disp, pred_depth = focal_x_baseline[b] / pred_disp (one IEEE division),
+ *             gt_depth; vmax = max_disp (0, 1) or depth_hi (3, 4).  Per pixel in float32, each operation rounded once:
+ *             v = mask ? x : -1; bad = (v == -1) -- an unmasked value that IS -1 too, a NaN not --; xa = (v / vmax) * 256 with
+ *             a true division; xa == 256 becomes 255; then, in this order: bad -> (255,0,0,255); xa NaN -> see flags;
+ *             xa < 0 -> table[0]; xa >= 256 -> table[255]; else table[(int)xa], truncating.  table: matplotlib's viridis as
+ *             (lut * 255).astype(uint8), alpha 255 (az_viridis_table.h).
+ *   flags     [B] int32, zeroed by the call itself on the stream: bit m of flags[b] is set when panel m (0, 1, 3, 4) of image b
+ *             has a bad pixel.  matplotlib paints an unmasked NaN as bad only when the image has NO masked pixel
+ *             (np.ma.is_masked false); otherwise NaN falls through astype(int) and take(mode="clip") to table[0].  So a NaN is
+ *             (255,0,0,255) where the panel's bit is clear and table[0] where it is set.
+ *   error     panels 2, 5: K19's classification with its table's integers as bytes, alpha 255 -- plt.imsave's
+ *             (c * 255).astype(uint8) of K19's float32 k / 255 is k --; panel 2: est = pred_disp, gt = gt_disp, disp_abs_thres,
+ *             disp_rel_thres; panel 5: est = fl(pred_depth * depth_scale), gt = fl(gt_depth * depth_scale), depth_abs_thres
+ *             (test.py:260 multiplies by 1000 in torch: both products and the difference are rounded once each, never
+ *             contracted); (0,0,0,255) where the mask is off or no row matches; K19's legend last.
+ * One call per batch, two launches (the flags, then the images), no allocation, no synchronisation.
+ * A required pointer null: AZ_ENULL; a non-positive B, H or W, pred_row_stride < W, a negative pred_img_stride, a max_disp or
+ * depth_hi that is not positive, out not 4-byte aligned: AZ_EINVAL -- all before any launch. */
+int az_result_images(uint8_t *out, int32_t *flags, const float *pred_disp, long long pred_row_stride,
+                     long long pred_img_stride, const float *gt_disp, const float *gt_depth, const uint8_t *mask,
+                     const float *focal_x_baseline, float max_disp, float depth_hi, float disp_abs_thres,
+                     float disp_rel_thres, float depth_scale, float depth_abs_thres, int B, int H, int W, void *stream);
+
 /* ---- K20: the loader's blur, colour jitter and normalisation (data side; az_augment.hip) -----
  * replaces datasets/dataset_utils.py:49-83 data_augmentation as datasets/messytable.py:264-280, 402-404 applies it: for a
  * grey image x in [0,1] whose three channels are equal until the last stage

@@ -28,7 +28,12 @@ torch fp32 operator chain (reflect F.pad, F.conv2d with the 2-D kernel, the blen
 times the real domain's resize (K21, Pillow's 8-bit BILINEAR, bit for bit) at B = 8, 720x1280 -> 540x960, whole and with the
 256x512 crop (100, 200), for uint8 and float32 output: the kernel, the copy probe (az_hbm_copy_probe) moving the same
 algorithmic bytes, and F.interpolate(mode="bilinear", antialias=True) on the float image (cropped afterwards) -- the nearest
-stock operator, which is not bit-compatible; the record says how many levels differ."""
+stock operator, which is not bit-compatible; the record says how many levels differ.
+
+    python tools/bench_aux_kernels.py result_images [out.json]
+times the six result images of a test batch (K24) at B = 1 and 4, 540x960: the launch plus its one copy against the host chain
+of test.py:235-272 up to the PNG encoder (four copies and matplotlib's to_rgba per image, two K19 images), and both kernels
+against the copy probe; profiles/result_images.json."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -682,6 +687,125 @@ def eval_epilogue(out_path=None):
             fh.write(json.dumps(doc, indent=1) + "\n")
 
 
+def result_images(out_path=None):
+    """K24 against the host chain it replaces (test.py:235-272 up to the PNG encoder, per image: four device-to-host copies,
+    [ground_mask] = -1, masked_where and matplotlib's to_rgba(bytes=True), and the two K19 error images copied to the host and
+    scaled to bytes), at B = 1 and B = 4, 540x960; equality first, then host wall time and kernel time.  Without matplotlib the
+    host chain is left out and the record says so."""
+    import importlib.util
+    import json
+    import statistics
+    import time
+    import numpy as np
+    import bench as _bench
+    from activezero_amd import ops
+    from activezero_amd.utils import error_images as ei
+    dev = torch.device("cuda:0")
+    H, W, reps, MAX_DISP = 540, 960, 20, 192
+    have_mpl = importlib.util.find_spec("matplotlib") is not None
+    probe = _bench.hbm_probe(dev)["GB/s"]
+    doc = {"case": "result_images", "copy_probe_GB/s": probe, "matplotlib": have_mpl,
+           "timing": "host wall time per call on rotated input sets, device drained before and after, median of %d; kernel time "
+                     "by events around one pass over the sets (together larger than the 256 MiB cache)" % reps}
+    if have_mpl:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.cm as mcm
+        import matplotlib.pyplot as plt
+        cmap = plt.get_cmap("viridis").copy()
+        cmap.set_bad(color="red")
+
+    def host_chain(d):
+        pred, gt_disp, gt_depth, mask, fb = d
+        pred_depth = fb.view(-1, 1, 1, 1) / pred
+        out = np.empty((pred.shape[0], 6, H, W, 4), np.uint8)
+        for b in range(pred.shape[0]):  # the reference has no batch
+            ground = torch.logical_not(mask[b, 0]).cpu().numpy()
+            for m, (x, vmax) in {0: (pred, MAX_DISP), 1: (gt_disp, MAX_DISP), 3: (pred_depth, 1.25), 4: (gt_depth, 1.25)}.items():
+                a = x[b, 0].detach().cpu().numpy()
+                a[ground] = -1
+                sm = mcm.ScalarMappable(cmap=cmap)
+                sm.set_clim(0, vmax)
+                out[b, m] = sm.to_rgba(np.ma.masked_where(a == -1, a), bytes=True)  # what plt.imsave hands to the encoder
+            s = slice(b, b + 1)
+            out[b, 2, :, :, :3] = (ei.disp_error_img(pred[s], gt_disp[s], mask[s]) * 255).astype(np.uint8)
+            out[b, 5, :, :, :3] = (ei.depth_error_img(pred_depth[s] * 1000, gt_depth[s] * 1000, mask[s]) * 255).astype(np.uint8)
+            out[b, 2, :, :, 3] = out[b, 5, :, :, 3] = 255
+        return out
+
+    def wall(fn, sets):
+        for i in range(min(sets, 2)):
+            fn(i)
+        us = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(sets):
+                fn(i)
+            torch.cuda.synchronize()
+            us.append((time.perf_counter() - t0) / sets * 1e6)
+        return {"us_per_call": statistics.median(us), "min_us": min(us)}
+
+    for B in (1, 4):
+        sets = 16 if B == 1 else 4  # 37 bytes per pixel and set: 307 MB in all
+        g = torch.Generator(device=dev).manual_seed(B)
+        data = []
+        for _ in range(sets):
+            gt_disp = (8 + 112 * torch.rand(B, 1, H, W, device=dev, generator=g)).contiguous()
+            pred = (gt_disp + 3 * torch.randn(B, 1, H, W, device=dev, generator=g)).contiguous()
+            fb = torch.full((B,), 446.31, device=dev) * torch.full((B,), 0.055, device=dev)
+            gt_depth = (fb.view(B, 1, 1, 1) / gt_disp).contiguous()
+            mask = torch.rand(B, 1, H, W, device=dev, generator=g) > 0.3
+            data.append((pred, gt_disp, gt_depth, mask, fb))
+
+        def fused(i):
+            return ops.result_images(*data[i][:4], data[i][4], MAX_DISP).cpu()  # the launch and ONE copy of finished bytes
+
+        rec = {"shape": [B, 6, H, W, 4]}
+        rec["k24_plus_one_copy"] = dict(wall(fused, sets), launches=3, host_syncs=1, bytes_to_host=24 * B * H * W,
+                                        launches_are="the memset of the flags, the flags kernel, the render kernel")
+        if have_mpl:
+            differ = int((fused(0).numpy() != host_chain(data[0])).any(-1).sum())
+            rec["pixels_that_differ_from_host_chain"] = differ  # (its depth is torch's own fb / pred on the device)
+            rec["host_chain"] = dict(wall(lambda i: host_chain(data[i]), sets), host_syncs=7 * B, bytes_to_host=(17 + 24) * B * H * W,
+                                     chain_is="per image: mask and four float maps copied, to_rgba(bytes=True) four times, two K19 images copied")
+            rec["speedup"] = rec["host_chain"]["us_per_call"] / rec["k24_plus_one_copy"]["us_per_call"]
+        outs = [torch.empty(B, 6, H, W, 4, dtype=torch.uint8, device=dev) for _ in range(sets)]
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+
+        def k24(i):
+            pred, gt_disp, gt_depth, mask, fb = data[i]
+            ops._call("az_result_images", outs[i].data_ptr(), flags.data_ptr(), pred.data_ptr(), W, H * W, gt_disp.data_ptr(),
+                      gt_depth.data_ptr(), mask.view(torch.uint8).data_ptr(), fb.data_ptr(), float(MAX_DISP), 1.25, 3.0, 0.05, 1000.0,
+                      1.0, B, H, W, ops._stream())
+
+        for _ in range(2):
+            for i in range(sets):
+                k24(i)
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(sets):
+                k24(i)
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / sets)
+        m = statistics.median(ms)
+        nbytes = 37.0 * B * H * W  # 13 read + 24 written per pixel; the flags kernel reads the 13 a first time
+        rec["k24_kernels"] = {"ms": m, "min_ms": min(ms), "algorithmic_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6,
+                              "of_copy_probe": nbytes / m / 1e6 / probe, "copy_probe_ms_for_these_bytes": nbytes / probe / 1e6,
+                              "includes": "the memset of the flags and both kernels; the flags kernel's 13 B/pixel are not counted"}
+        doc["B%d" % B] = rec
+        del data, outs
+    print(json.dumps(doc))
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(doc, indent=1) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "result_images":
+    result_images(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "eval_epilogue":
     eval_epilogue(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
