@@ -6,10 +6,14 @@ projector exposures, made per item on the device instead of by a pass over the d
 augment_images / data_augmentation are the twin of data_augmentation (dataset_utils.py:49-83: GaussianBlur, ColorJitter,
 ToTensor, Normalize) on az_augment (csrc/az_augment.hip): a batch of grey images in, normalised 3-channel images out.
 resize_bilinear is the twin of the PIL resize the real item goes through (messytable.py:324-341, 353-356, 410-420) on
-az_resize_bilinear_u8 (csrc/az_resample.hip): 8-bit grey images in, PIL's bits out, cropped on the way if asked."""
+az_resize_bilinear_u8 (csrc/az_resample.hip): 8-bit grey images in, PIL's bits out, cropped on the way if asked.
+depth_to_labels is the twin of the loader's depth lines (messytable.py:197-213, 256-261, 281-284) on az_depth_labels
+(csrc/az_test_inputs.hip): raw millimetre maps in, the four float32 disparity and depth labels out; stereo_constants gives
+the two host scalars it needs from an item's metadata."""
+import numpy as np
 import torch
 
-from activezero_amd import _lib
+from activezero_amd import _lib, ops
 from activezero_amd.ops import _call, _chk, _p, _stream
 
 
@@ -189,6 +193,45 @@ def resize_bilinear(grey, size, crop=None, dtype=torch.uint8):
         _call("az_resize_bilinear_u8", _p(u8), _p(f32), _p(g), _p(table_y), _p(table_x), n, hin, win, hout, wout, y0, x0,
               h, w, _stream())
     return out[0] if grey.dim() == 2 else out
+
+
+def stereo_constants(extrinsic_l, extrinsic_r, intrinsic_l):
+    """messytable.py:205-206: (focal_length, baseline) of an item's metadata as float64 host scalars -- the focal length of
+    the left IR camera at half resolution, intrinsic_l[0, 0] / 2, and the distance between the two IR cameras, the norm of the
+    difference of the extrinsics' last columns.  Host arithmetic on a 3 x 3 and two 4 x 4 matrices: no device is touched."""
+    extrinsic_l, extrinsic_r, intrinsic_l = (np.asarray(m, dtype=np.float64) for m in (extrinsic_l, extrinsic_r, intrinsic_l))
+    baseline = np.linalg.norm(extrinsic_l[:, -1] - extrinsic_r[:, -1])
+    focal_length = intrinsic_l[0, 0] / 2
+    return focal_length, baseline
+
+
+def depth_to_labels(depth_l_mm, depth_r_mm, focal_length, baseline, crop=None):
+    """messytable.py:197-213, 256-261, 281-284 on az_depth_labels (csrc/az_test_inputs.hip): the two raw millimetre depth maps
+    of a batch, [H2,W2] or [B,H2,W2] uint16 (a 16-bit PNG) or int32 (PIL's mode I) CUDA tensors -- uploaded as they are, a
+    quarter of the bytes of the four float maps the reference's loader uploads -- -> (img_disp_l, img_depth_l, img_disp_r,
+    img_depth_r), each [1,h2,w2] or [B,1,h2,w2] float32 with the bits of the reference's float64 arithmetic.  focal_length,
+    baseline: stereo_constants' numbers, or B values on the device.  crop None: the whole maps (test mode); (y0, x0, h2, w2)
+    integers: that window of every item; (origin, (h2, w2)) with origin an int32 [B,2] CUDA tensor of (y0, x0): a window per
+    item -- the reference's 2x : 2(x + th), 2y : 2(y + tw) with y0 = 2x, x0 = 2y, h2 = 2th, w2 = 2tw.  Nothing synchronises."""
+    if not isinstance(depth_l_mm, torch.Tensor) or not isinstance(depth_r_mm, torch.Tensor):
+        raise TypeError("depth_l_mm, depth_r_mm: expected tensors")
+    if depth_l_mm.dim() not in (2, 3):
+        raise RuntimeError("depth_l_mm must be [H2,W2] or [B,H2,W2]")
+    single = depth_l_mm.dim() == 2
+    a, b_ = ((t[None] if single else t).contiguous() for t in (depth_l_mm, depth_r_mm))
+    origin = window = None
+    if crop is not None and len(crop) == 4:
+        y0, x0, h2, w2 = (int(c) for c in crop)
+        if y0 < 0 or x0 < 0 or h2 <= 0 or w2 <= 0 or y0 + h2 > a.shape[-2] or x0 + w2 > a.shape[-1]:
+            raise RuntimeError(f"crop {(y0, x0, h2, w2)} lies outside the {a.shape[-2]} x {a.shape[-1]} map")
+        origin = torch.empty(a.shape[0], 2, dtype=torch.int32, device=a.device)  # filled on the device: no host round trip
+        origin[:, 0].fill_(y0)
+        origin[:, 1].fill_(x0)
+        window = (h2, w2)
+    elif crop is not None:
+        origin, window = crop
+    outs = ops.depth_labels(a, b_, focal_length, baseline, origin, window)
+    return tuple(o[0] for o in outs) if single else outs
 
 
 class _Augmentation:

@@ -544,6 +544,90 @@ def result_images(pred_disp, gt_disp, gt_depth, mask, focal_x_baseline, max_disp
 
 
 # ----------------------------------------------------------------------------
+# K25 millimetre depth maps to labels, K26 a test item's network inputs
+# ----------------------------------------------------------------------------
+_DEPTH_DTYPES = {torch.uint16: "AZ_DEPTH_U16", torch.int32: "AZ_DEPTH_I32"}
+
+
+def _per_item_f64(value, b, name, device):
+    """one float64 per item on the device, from a number (filled on the device: no host round trip) or a tensor of B values"""
+    if isinstance(value, torch.Tensor):
+        if value.device != device:
+            raise RuntimeError(f"{name}: must live on the device of the depth maps ({device}), got {value.device}")
+        if value.numel() != b:
+            raise RuntimeError(f"{name}: expected {b} values (one per item), got {value.numel()}")
+        return value.reshape(b).to(torch.float64).contiguous()
+    return torch.full((b,), float(value), dtype=torch.float64, device=device)
+
+
+def depth_labels(depth_l_mm, depth_r_mm, focal_length, baseline, origin=None, window=None):
+    """messytable.py:197-213, 256-261, 281-284 in one launch: depth_l_mm, depth_r_mm [B,H2,W2] raw millimetres, uint16 or
+    int32; focal_length, baseline a number or B values on the device (taken as float64) -> (disp_l, depth_l, disp_r, depth_r),
+    each [B,1,h2,w2] float32 with numpy's bits: depth = v / 1000 and disp = focal_length * baseline / depth where v > 0, else
+    0, in float64, rounded once.  origin None: the whole map; or int32 [B,2] on the device, (y0, x0) per item, with window =
+    (h2, w2): the training crop, clamped into the map on the device.  No host sync."""
+    if not isinstance(depth_l_mm, torch.Tensor) or depth_l_mm.dtype not in _DEPTH_DTYPES:
+        raise RuntimeError("depth_l_mm: expected a torch.uint16 or torch.int32 tensor")
+    a = _chk(depth_l_mm, "depth_l_mm", depth_l_mm.dtype)
+    b_ = _chk(depth_r_mm, "depth_r_mm", a.dtype)
+    if a.dim() != 3 or a.numel() == 0 or b_.shape != a.shape or b_.device != a.device:
+        raise RuntimeError("depth_l_mm and depth_r_mm must be non-empty [B,H2,W2] of one shape on one device")
+    n, hh, ww = a.shape
+    if origin is None:
+        if window is not None and tuple(int(s) for s in window) != (hh, ww):
+            raise RuntimeError("window needs an origin")
+        h2, w2 = hh, ww
+    else:
+        if window is None:
+            raise RuntimeError("origin needs a window size (h2, w2)")
+        h2, w2 = (int(s) for s in window)
+        if not 0 < h2 <= hh or not 0 < w2 <= ww:
+            raise RuntimeError(f"window {(h2, w2)} does not fit the {hh} x {ww} map")
+        origin = _chk(origin, "origin", torch.int32)
+        if tuple(origin.shape) != (n, 2) or origin.device != a.device:
+            raise RuntimeError(f"origin: expected int32 [{n},2] on {a.device}, got {tuple(origin.shape)} on {origin.device}")
+    fl = _per_item_f64(focal_length, n, "focal_length", a.device)
+    bl = _per_item_f64(baseline, n, "baseline", a.device)
+    outs = [torch.empty(n, 1, h2, w2, dtype=torch.float32, device=a.device) for _ in range(4)]
+    with torch.cuda.device(a.device):
+        _call("az_depth_labels", *(_p(o) for o in outs), _p(a), _p(b_), _lib.CONST[_DEPTH_DTYPES[a.dtype]], _p(fl), _p(bl),
+              _p(origin), n, hh, ww, h2, w2, _stream())
+    return tuple(outs)
+
+
+def test_images(src, src_second=None, size=None, pad=(0, 0)):
+    """test.py:118-131, 141-146 in one launch: src (and src_second, the other view, of the same form) either [N,3,Hin,Win]
+    float32, normalised, or [N,Hin,Win] uint8 grey levels, normalised per tap as augment_images normalises them -> float32
+    [N (+ N_second),3,H + top,W + right]: ATen's bilinear resize (align_corners=False) to size = (H, W) -- None: the
+    source's size, the image is only padded -- below `top` rows and left of `right` columns of +0.0, pad = (top, right).
+    src's images come first.  No host sync."""
+    if not isinstance(src, torch.Tensor) or src.dtype not in (torch.float32, torch.uint8):
+        raise RuntimeError("src: expected a torch.float32 or torch.uint8 tensor")
+    u8 = src.dtype == torch.uint8
+    srcs = [_chk(src, "src", src.dtype)] + ([] if src_second is None else [_chk(src_second, "src_second", src.dtype)])
+    for t in srcs:
+        if t.dim() != (3 if u8 else 4) or (not u8 and t.shape[1] != 3) or t.numel() == 0:
+            raise RuntimeError(f"a source of {src.dtype} must be a non-empty {'[N,Hin,Win]' if u8 else '[N,3,Hin,Win]'}, got "
+                               f"{tuple(t.shape)}")
+        if t.shape[-2:] != src.shape[-2:] or t.device != src.device:
+            raise RuntimeError("src and src_second must have one image size and one device")
+    hin, win = src.shape[-2:]
+    h, w = (hin, win) if size is None else (int(s) for s in size)
+    top, right = (int(s) for s in pad)
+    if h < 1 or w < 1 or top < 0 or right < 0:
+        raise RuntimeError(f"size {(h, w)} must be positive and pad {(top, right)} non-negative")
+    n, n2 = srcs[0].shape[0], (srcs[1].shape[0] if len(srcs) == 2 else 0)
+    out = torch.empty(n + n2, 3, h + top, w + right, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _call("az_test_images", _p(out), _p(srcs[0]), _p(srcs[1]) if n2 else None, int(u8), n, n2, hin, win, h, w, top,
+              right, _stream())
+    return out
+
+
+test_images.__test__ = False  # (pytest would collect a function of this name from a test module that imports it)
+
+
+# ----------------------------------------------------------------------------
 # K15 RAFT-Stereo convex upsampling
 # ----------------------------------------------------------------------------
 def _chk_mask(mask, name="mask"):

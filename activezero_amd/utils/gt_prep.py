@@ -10,7 +10,9 @@ An addition, not a shadow of a reference module.  Opt in inside train_sample (tr
     disp_gt_l, depth_gt, mask = prepare_sim_gt(sample, cfg.MODEL.MAX_DISP)
 
 in place of train.py:248-249, 255-272, and in test.py with `prepare_test_gt(data)` in place of :82-85, 91-110 and
-`prepare_test_mask(...)` (the fused K23 kernel, az_eval_mask) in place of the mask lines :112-117, 162-193.
+`prepare_test_mask(...)` (the fused K23 kernel, az_eval_mask) in place of the mask lines :112-117, 162-193, and
+`img_L, img_R = prepare_test_images(img_L, img_R)` (the fused K26 kernel, az_test_images) in place of the bilinear resizes and
+pads of the network's inputs, :118-131, 141-146.
 """
 import torch
 
@@ -51,6 +53,22 @@ def prepare_test_gt(sample_or_tensors, size=(540, 960), device=None, check=False
         label = label.to(torch.float32)
     img_disp_l, img_depth_l, label_s, _, _ = ops.gt_from_right(disp_r, extra=depth_r, keep=label, size=size, check=check)
     return img_disp_l, img_depth_l, label_s.type(torch.int)
+
+
+def prepare_test_images(img_L, img_R, size=(540, 960), pad_to=(544, 960)):
+    """test.py:118-131, 141-146: the two views of a test batch -> img_L, img_R [B,3,pad_to[0],pad_to[1]] float32, resized to
+    `size` with F.interpolate(mode="bilinear", align_corners=False)'s arithmetic and padded at the top and on the right with
+    zeros, in ONE launch of the fused K26 kernel (az_test_images) for both views.  Each view is [B,3,Hin,Win] float32 as the
+    loader normalised it (data["img_real_L"], or data["img_sim_L"], which is already at `size` and is only padded), or
+    [B,Hin,Win] uint8 grey levels, normalised on the way as the loader would have.  The results are the two halves of one
+    tensor.  Nothing synchronises."""
+    (h, w), (hp, wp) = (int(s) for s in size), (int(s) for s in pad_to)
+    if hp < h or wp < w:
+        raise RuntimeError(f"pad_to {(hp, wp)} is smaller than size {(h, w)}")
+    device = next((t.device for t in (img_L, img_R) if t.device.type == "cuda"), None) or torch.device("cuda")
+    img_L, img_R = img_L.to(device).contiguous(), img_R.to(device).contiguous()
+    out = ops.test_images(img_L, img_R, size=(h, w), pad=(hp - h, wp - w))
+    return out[:img_L.shape[0]], out[img_L.shape[0]:]
 
 
 def prepare_test_mask(img_disp_l, img_depth_l, max_disp, exclude_bg=True, robot_mask=None, realsense_depth=None, depth_hi=1.25):

@@ -680,6 +680,49 @@ int az_result_images(uint8_t *out, int32_t *flags, const float *pred_disp, long 
                      const float *focal_x_baseline, float max_disp, float depth_hi, float disp_abs_thres,
                      float disp_rel_thres, float depth_scale, float depth_abs_thres, int B, int H, int W, void *stream);
 
+/* ---- K25: millimetre depth maps to disparity and depth labels (az_test_inputs.hip) --------------------------------
+ * replaces datasets/messytable.py:197-198, 208-213, 256-261, 281-284 (the same lines in messytable_test.py): two 16-bit
+ * millimetre maps divided by 1000 in float64, focal_length * baseline / depth under a mask in float64, the training crop
+ * 2x : 2(x + th), four casts to float32 and the upload of the four float maps -- the raw maps are uploaded instead, a
+ * quarter of the bytes, and one launch writes the four labels.
+ * mm_l, mm_r [B,H2,W2] raw millimetres of type `dtype`: AZ_DEPTH_U16 uint16 (what a 16-bit PNG decodes to) or AZ_DEPTH_I32
+ * int32 (Pillow's mode I); focal_length, baseline [B] f64 ON THE DEVICE (messytable.py:205-206 are float64 scalars).
+ * origin: NULL -- the whole map, test mode: (h2, w2) must be (H2, W2) -- or [B,2] int32 ON THE DEVICE, (y0, x0) per item in
+ * the maps' own pixels, the window [y0, y0 + h2) x [x0, x0 + w2).  A device-side origin cannot be refused without a
+ * synchronisation, so it has a meaning instead: it is clamped into [0, H2 - h2] x [0, W2 - w2], the window never leaves
+ * the map.  Outputs disp_l, depth_l, disp_r, depth_r, each [B,1,h2,w2] f32, fully written.  Per pixel, bit for bit numpy:
+ *   z = (double)v / 1000.0;  fb = focal_length[b] * baseline[b] in double;  depth = (float)z;
+ *   disp = v > 0 ? (float)(fb / z) : 0       IEEE double divisions, nothing contracted, each result rounded to f32 once
+ * so a non-positive int32 value gives disparity 0 and depth v / 1000.
+ * A required pointer null: AZ_ENULL; another dtype code, a non-positive size, a window larger than the map, no origin with a
+ * window that is not the map: AZ_EINVAL; more than 2^47 / ceil(w2 / 4) rows: AZ_EUNSUPPORTED -- all before any launch. */
+#define AZ_DEPTH_U16 0
+#define AZ_DEPTH_I32 1
+int az_depth_labels(float *disp_l, float *depth_l, float *disp_r, float *depth_r, const void *mm_l, const void *mm_r,
+                    int dtype, const double *focal_length, const double *baseline, const int32_t *origin, int B, int H2,
+                    int W2, int h2, int w2, void *stream);
+
+/* ---- K26: a test item's network inputs: normalise, bilinear resize and pad (az_test_inputs.hip) -------------------
+ * replaces test.py:118-131, 141-146: F.interpolate(mode="bilinear", align_corners=False) and F.pad(top, right) for either
+ * view, four launches and four intermediates -- one launch for both views, the padded tensor written once.
+ * src [N,...], and src_second [N_second,...] of the same form or NULL with N_second = 0 (the right view: the two need not
+ * be stacked first); the output holds src's images, then src_second's:
+ *   src_is_u8 = 0   [n,3,Hin,Win] f32, normalised as the reference's loader delivers it
+ *   src_is_u8 = 1   [n,Hin,Win] uint8 grey levels; every tap is normalised per channel with K20's operations and bits:
+ *                   float32 v / 255, minus the ImageNet mean, divided by the std, each division correctly rounded
+ * out [N + N_second,3,H + top_pad,W + right_pad] f32, fully written: the resized image at rows top_pad.., columns 0..W,
+ * every pad element +0.0.  The resize is ATen's upsample_bilinear2d, align_corners=False, no antialiasing, either
+ * direction; per axis in float32, every operation rounded on its own (no fma):
+ *   scale = (float)in / out;  s = max(scale * (dst + 0.5f) - 0.5f, 0);  i0 = (int)s;  i1 = i0 + (i0 < in - 1);
+ *   l1 = s - i0;  l0 = 1 - l1
+ *   value = l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d),   a, b = row i0h at i0w, i1w;  c, d = row i1h
+ * in == out has no path of its own: the formula returns a finite input unchanged (the sim branch only pads); a tap that is
+ * not finite follows IEEE as ATen's does (0 * inf = NaN) and never reaches a pad element.
+ * out or a needed source null: AZ_ENULL; a non-positive size, a negative pad or N_second, another src_is_u8: AZ_EINVAL; a
+ * padded size or image count beyond 2^31 - 1: AZ_EUNSUPPORTED -- all before any launch. */
+int az_test_images(float *out, const void *src, const void *src_second, int src_is_u8, int N, int N_second, int Hin,
+                   int Win, int H, int W, int top_pad, int right_pad, void *stream);
+
 /* ---- K20: the loader's blur, colour jitter and normalisation (data side; az_augment.hip) -----
  * replaces datasets/dataset_utils.py:49-83 data_augmentation as datasets/messytable.py:264-280, 402-404 applies it: for a
  * grey image x in [0,1] whose three channels are equal until the last stage

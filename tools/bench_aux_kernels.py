@@ -33,7 +33,13 @@ stock operator, which is not bit-compatible; the record says how many levels dif
     python tools/bench_aux_kernels.py result_images [out.json]
 times the six result images of a test batch (K24) at B = 1 and 4, 540x960: the launch plus its one copy against the host chain
 of test.py:235-272 up to the PNG encoder (four copies and matplotlib's to_rgba per image, two K19 images), and both kernels
-against the copy probe; profiles/result_images.json."""
+against the copy probe; profiles/result_images.json.
+
+    python tools/bench_aux_kernels.py test_inputs [out.json]
+times a test item's labels (K25, B = 1 and 4, 1080x1920 uint16 maps) and network inputs (K26, N = 2 and 8, 720x1280 -> 540x960,
+pad (4, 0), float and grey-level sources): each kernel against the copy probe moving the same bytes and against what it
+replaces -- F.interpolate + F.pad per view on the device for K26, the loader's numpy lines plus the upload of the four float
+maps for K25; profiles/test_inputs.json.  Recorded, not gated."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -803,6 +809,156 @@ def result_images(out_path=None):
             fh.write(json.dumps(doc, indent=1) + "\n")
 
 
+def test_inputs(out_path=None):
+    """K25 (B = 1 and 4, 1080x1920 uint16 maps) and K26 (N = 2 and 8, 720x1280 -> 540x960, pad (4, 0), both source forms):
+    each kernel by events on rotated buffer sets against the copy probe moving the same algorithmic bytes, and against what it
+    replaces -- for K26 the device chain of test.py:118-146 (F.interpolate and F.pad per view) by events, for K25 the loader's
+    numpy lines plus the upload of their four float maps, by host wall time against the upload of the raw maps plus the
+    launch.  Equality with the replaced chain is checked first."""
+    import json
+    import statistics
+    import time
+    import numpy as np
+    import torch.nn.functional as F
+    from activezero_amd import ops
+    from activezero_amd.datasets import dataset_utils_gpu as du
+    dev = torch.device("cuda:0")
+    reps = 20
+    doc = {"case": "test_inputs",
+           "timing": "kernels: one call per buffer set, the sets rotated (together more than the 256 MiB cache), per event pair, "
+                     "median of %d after two warm-up rounds; the copy probe moves the same number of bytes (half in, half out) "
+                     "through the same rotation; host chains: wall time per call, device drained before and after, median of 5" % reps}
+
+    def events(fn, sets):
+        for _ in range(2):
+            for i in range(sets):
+                fn(i)
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(sets):
+                fn(i)
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / sets)
+        return statistics.median(ms), min(ms)
+
+    def wall(fn):
+        fn()
+        ms = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ms)
+
+    def probe(nbytes, sets):
+        nf = int(nbytes) // 8  # floats the probe copies: 4 bytes in + 4 bytes out each
+        src = [torch.empty(nf, device=dev).normal_() for _ in range(sets)]
+        dst = [torch.empty(nf, device=dev) for _ in range(sets)]
+        return events(lambda i: ops._call("az_hbm_copy_probe", dst[i].data_ptr(), src[i].data_ptr(), nf, ops._stream()), sets)
+
+    def sets_for(per_set):
+        return max(2, -(-300 * (1 << 20) // per_set))
+
+    # ---- K25
+    H2, W2, FOCAL, BASE = 1080, 1920, 446.31, 0.055
+    rng = np.random.default_rng(0)
+    for B in (1, 4):
+        nbytes = float(B) * H2 * W2 * (2 * 2 + 4 * 4)
+        sets = sets_for(int(nbytes))
+        host = [rng.integers(0, 2000, (2, B, H2, W2)).astype(np.uint16) for _ in range(2)]
+        mm = [torch.from_numpy(host[i % 2]).to(dev) for i in range(sets)]
+        fl = torch.full((B,), FOCAL, dtype=torch.float64, device=dev)
+        bl = torch.full((B,), BASE, dtype=torch.float64, device=dev)
+        outs = [[torch.empty(B, 1, H2, W2, device=dev) for _ in range(4)] for _ in range(sets)]
+
+        def k25(i):
+            ops._call("az_depth_labels", *(o.data_ptr() for o in outs[i]), mm[i][0].data_ptr(), mm[i][1].data_ptr(), 0,
+                      fl.data_ptr(), bl.data_ptr(), None, B, H2, W2, H2, W2, ops._stream())
+
+        def numpy_chain(maps=host[0]):  # messytable.py:197-213, 281-284 per item, then the four uploads
+            items = []
+            for b in range(B):
+                item = []
+                for side in (0, 1):
+                    depth = np.array(maps[side, b]) / 1000
+                    mask = depth > 0
+                    disp = np.zeros_like(depth)
+                    disp[mask] = FOCAL * BASE / depth[mask]
+                    item += [torch.tensor(disp, dtype=torch.float32).unsqueeze(0), torch.tensor(depth, dtype=torch.float32).unsqueeze(0)]
+                items.append(item)
+            return [torch.stack([it[k] for it in items]).to(dev) for k in range(4)]
+
+        def raw_upload(maps=host[0]):
+            return du.depth_to_labels(torch.from_numpy(maps[0]).to(dev), torch.from_numpy(maps[1]).to(dev), FOCAL, BASE)
+
+        k25(0)
+        assert all(torch.equal(a, b) for a, b in zip(outs[0], numpy_chain()))
+        m, lo = events(k25, sets)
+        pm, plo = probe(nbytes, sets)
+        doc["k25_B%d" % B] = {
+            "maps": [B, H2, W2], "ms": m, "min_ms": lo, "algorithmic_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6,
+            "copy_probe_ms_same_bytes": pm, "copy_probe_min_ms": plo, "of_copy_probe": pm / m, "buffer_sets": sets,
+            "numpy_lines_plus_upload_ms": wall(numpy_chain), "raw_upload_plus_k25_ms": wall(raw_upload),
+            "upload_MB": {"float_labels": 16.0 * B * H2 * W2 / 1e6, "raw_uint16": 4.0 * B * H2 * W2 / 1e6}}
+        del mm, outs
+
+    # ---- K26
+    Hin, Win, H, W, top, right = 720, 1280, 540, 960, 4, 0
+    g = torch.Generator(device=dev).manual_seed(0)
+    for N in (2, 8):
+        for name, u8 in (("float", 0), ("levels", 1)):
+            in_bytes = N * Hin * Win * (1 if u8 else 12)
+            nbytes = float(in_bytes + N * 3 * (H + top) * (W + right) * 4)
+            sets = sets_for(int(nbytes))
+            levels = [torch.randint(0, 256, (N, Hin, Win), device=dev, generator=g, dtype=torch.uint8) for _ in range(sets)]
+            srcs = levels if u8 else [du.augment_images(l) for l in levels]
+            outs = [torch.empty(N, 3, H + top, W + right, device=dev) for _ in range(sets)]
+
+            def k26(i):
+                ops._call("az_test_images", outs[i].data_ptr(), srcs[i].data_ptr(), None, u8, N, 0, Hin, Win, H, W, top, right,
+                          ops._stream())
+
+            rec = {"images": N, "in": [Hin, Win], "out": [H + top, W + right], "buffer_sets": sets}
+            k26(0)
+            if not u8:
+                floats = srcs
+
+                def chain(i):  # test.py:118-146: the two views on their own
+                    res = []
+                    for view in (floats[i][:N // 2], floats[i][N // 2:]):
+                        x = F.interpolate(view, (H, W), mode="bilinear", recompute_scale_factor=False, align_corners=False)
+                        res.append(F.pad(x, (0, right, top, 0, 0, 0, 0, 0), mode="constant", value=0))
+                    return res
+
+                rec["max_abs_diff_vs_chain"] = float((outs[0] - torch.cat(chain(0))).abs().max())
+                rec["largest_tap"] = float(floats[0].abs().max())
+                assert rec["max_abs_diff_vs_chain"] <= 12 * rec["largest_tap"] * 2.0 ** -24  # two float32 blends, 6 M 2^-24 each
+                cm, clo = events(chain, sets)
+                rec.update({"chain_ms": cm, "chain_min_ms": clo, "chain_launches": 4})
+            else:
+                assert torch.equal(outs[0], ops.test_images(du.augment_images(levels[0]), size=(H, W), pad=(top, right)))
+            m, lo = events(k26, sets)
+            pm, plo = probe(nbytes, sets)
+            rec.update({"ms": m, "min_ms": lo, "algorithmic_MB": nbytes / 1e6, "GB/s": nbytes / m / 1e6,
+                        "copy_probe_ms_same_bytes": pm, "copy_probe_min_ms": plo, "of_copy_probe": pm / m})
+            if "chain_ms" in rec:
+                rec["speedup_vs_chain"] = rec["chain_ms"] / m
+            doc["k26_N%d_%s" % (N, name)] = rec
+            del levels, srcs, outs
+    print(json.dumps(doc))
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(doc, indent=1) + "\n")
+
+
+test_inputs.__test__ = False  # (a benchmark, not a test)
+if len(sys.argv) > 1 and sys.argv[1] == "test_inputs":
+    test_inputs(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "result_images":
     result_images(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
