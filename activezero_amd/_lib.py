@@ -107,6 +107,7 @@ def parse_header(text):
 with open(HEADER) as _f:
     _SIGS, _RESTYPE, CONST, _STRUCTS = parse_header(_f.read())
 PACK_DESC, UNPACK_DESC, ABSMAX_DESC = _STRUCTS["AzPackDesc"], _STRUCTS["AzUnpackDesc"], _STRUCTS["AzAbsmaxDesc"]
+ADAM_DESC = _STRUCTS["AzAdamDesc"]
 
 
 def declared_symbols():

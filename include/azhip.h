@@ -904,6 +904,52 @@ int az_costconv_assemble_fwd(float *out, const float *F_bulk, const float *F_edg
 int az_costconv_assemble_bwd(float *dF_bulk, float *dF_edge, float *dG, const float *grad_out, int B, int D,
                              int H, int W, void *stream);
 
+/* ---- K27/K28: the optimizer step -- Adam / AdamW over all tensors of a parameter group in one launch, with the global
+ * gradient norm, clip_grad_norm_'s coefficient, GradScaler's inverse scale and its skip on non-finite gradients folded in
+ * (activezero_amd/optim.py).  One descriptor per tensor that has a gradient; `step` is torch's per-parameter step count, a
+ * float32 scalar in device memory.  descs in DEVICE memory; block_desc / first_block as for az_pack_f16_multi above with
+ * one workgroup per 1024 elements of one tensor ((n + 3) / 4 work items of four floats, 256 per workgroup), nblocks in all.
+ * Hyper-parameters are arguments, not members: every tensor of a call shares them.
+ *
+ * az_grad_sumsq_multi (K27): partials[b] = the sum over workgroup b's elements of grad^2, every square and every addition
+ *   in fp64 (the square of a float is exact in fp64), in a fixed order, one plain store per workgroup: no atomics, the same
+ *   bits on every run.  An inf / NaN gradient makes its partial inf / NaN.
+ * az_optim_begin: one workgroup.  sum = partials[0 .. nblocks_norm) added in a fixed order in fp64 (the partials of SEVERAL
+ *   az_grad_sumsq_multi calls may lie behind one another: one norm over all of them), then in fp64
+ *       inv_scale  = grad_scale ? 1 / grad_scale[0] : 1
+ *       total_norm = sqrt(sum) * inv_scale
+ *       clip_coef  = max_norm >= 0 ? min(1, max_norm / (total_norm + 1e-6)) : 1      (torch's clip_grad_norm_)
+ *       skip       = !isfinite(sum) || (found_inf && found_inf[0] != 0)
+ *   head[0..4) = {total_norm, inv_scale * clip_coef, skip ? 1 : 0, clip_coef} as floats.  Unless skipping, every descriptor's
+ *   step becomes step + 1 and rec[2 i], rec[2 i + 1] = lr / (1 - beta1^step), sqrt(1 - beta2^step) of descriptor i, computed
+ *   in fp64, stored as floats.  nblocks_norm == 0 (partials may be NULL): no norm was taken, total_norm = 0, the multiplier
+ *   is inv_scale, and only found_inf can skip.
+ * az_adam_multi (K28): returns at once when head[2] != 0 -- no parameter, moment or step of any tensor is written.  Otherwise
+ *   per element in fp32, in the order of torch's _single_tensor_adam:
+ *       g' = use_mult ? g * head[1] : g
+ *       coupled decay (decoupled == 0):  g' += weight_decay * p;     decoupled:  p *= 1 - lr * weight_decay
+ *       m += (1 - beta1) * (g' - m);     v = beta2 * v + (1 - beta2) * g' * g'
+ *       p -= rec[2 i] * m / (sqrt(v) / rec[2 i + 1] + eps)
+ *   The gradient is read only: it is NOT left unscaled or clipped in memory, unlike clip_grad_norm_ and unscale_.  16-byte
+ *   accesses when all four tensors of a descriptor are 16-byte aligned, scalar ones otherwise and for the last n & 3
+ *   elements.  0 <= beta1, beta2 < 1; lr, eps, weight_decay >= 0. */
+typedef struct AzAdamDesc {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    float *step;
+    long long n;
+} AzAdamDesc;
+int az_grad_sumsq_multi(double *partials, const AzAdamDesc *descs, const int *block_desc, const int *first_block, int nd,
+                        int nblocks, void *stream);
+int az_optim_begin(float *head, float *rec, const AzAdamDesc *descs, int nd, const double *partials, int nblocks_norm,
+                   const float *grad_scale, const float *found_inf, double lr, double beta1, double beta2, double max_norm,
+                   void *stream);
+int az_adam_multi(const AzAdamDesc *descs, const int *block_desc, const int *first_block, int nd, int nblocks,
+                  const float *head, const float *rec, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int decoupled, int use_mult, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,14 @@ against the copy probe; profiles/result_images.json.
 times a test item's labels (K25, B = 1 and 4, 1080x1920 uint16 maps) and network inputs (K26, N = 2 and 8, 720x1280 -> 540x960,
 pad (4, 0), float and grey-level sources): each kernel against the copy probe moving the same bytes and against what it
 replaces -- F.interpolate + F.pad per view on the device for K26, the loader's numpy lines plus the upload of the four float
-maps for K25; profiles/test_inputs.json.  Recorded, not gated."""
+maps for K25; profiles/test_inputs.json.  Recorded, not gated.
+
+    python tools/bench_aux_kernels.py optim [out.json]
+times the optimizer step on the full-size PSMNet parameter set (maxdisp 192) with synthetic gradients: torch.optim.Adam in
+its default (foreach) and fused=True forms, activezero_amd.optim.FusedAdam (K28) without and with max_grad_norm=1.0 (K27), and
+foreach Adam behind clip_grad_norm_, beside the copy probe moving the update's 28 B per parameter; back to back (the 80 MB of
+p, g, m, v stay in the 256 MiB cache) and behind a 512 MiB fill (they arrive from HBM, as in a training step);
+profiles/optim_step.json.  Recorded, not gated."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -955,7 +962,93 @@ def test_inputs(out_path=None):
             fh.write(json.dumps(doc, indent=1) + "\n")
 
 
+
+def optim_step(out_path=None):
+    import statistics
+    import time
+    from activezero_amd import ops
+    from activezero_amd.nets.psmnet.psmnet_3 import PSMNet
+    from activezero_amd.optim import FusedAdam
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    shapes = [tuple(p.shape) for p in PSMNet(192).parameters()]
+    n_param = sum(int(torch.Size(s).numel()) for s in shapes)
+    g = torch.Generator(device=dev).manual_seed(1)
+
+    def make(ctor, clip=False):
+        ps = [torch.nn.Parameter(0.1 * torch.randn(s, device=dev, generator=g)) for s in shapes]
+        for p in ps:
+            p.grad = 1e-3 * torch.randn(p.shape, device=dev, generator=g)
+        opt = ctor(ps)
+        if clip:
+            return lambda: (torch.nn.utils.clip_grad_norm_(ps, 1.0), opt.step()), opt
+        return opt.step, opt
+
+    variants = {
+        "torch_adam_foreach": make(lambda ps: torch.optim.Adam(ps, lr=2e-4)),
+        "torch_adam_fused": make(lambda ps: torch.optim.Adam(ps, lr=2e-4, fused=True)),
+        "fused_adam": make(lambda ps: FusedAdam(ps, lr=2e-4)),
+        "fused_adam_max_grad_norm": make(lambda ps: FusedAdam(ps, lr=2e-4, max_grad_norm=1.0)),
+        "torch_adam_foreach_plus_clip_grad_norm": make(lambda ps: torch.optim.Adam(ps, lr=2e-4), clip=True),
+    }
+    n_copy = (int(3.5 * n_param) + 3) // 4 * 4  # a float copied is 8 bytes moved: 28 B per parameter
+    src, dst = torch.randn(n_copy, device=dev, generator=g), torch.empty(n_copy, device=dev)
+    variants["copy_probe_28B_per_param"] = (
+        lambda: ops._call("az_hbm_copy_probe", dst.data_ptr(), src.data_ptr(), n_copy, ops._stream()), None)
+    flush = torch.empty(1 << 27, device=dev)  # 512 MiB: twice the Infinity Cache
+    inner, reps = 10, 15
+    for fn, _ in variants.values():
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    warm = {k: [] for k in variants}
+    cold_wall, cold_dev = {k: [] for k in variants}, {k: [] for k in variants}
+    for _ in range(reps):  # the variants alternate inside every repetition: drift hits all of them alike
+        for k, (fn, _) in variants.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(inner):
+                fn()
+            torch.cuda.synchronize()
+            warm[k].append((time.perf_counter() - t0) / inner * 1e3)
+            flush.fill_(1.0)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            cold_wall[k].append((time.perf_counter() - t0) * 1e3)
+            cold_dev[k].append(a.elapsed_time(b))
+    med = statistics.median
+    rec = {"case": "optim_step", "tensors": len(shapes), "parameters": n_param, "bytes_per_step_MB": 28.0 * n_param / 1e6,
+           "timing": "ms per step.  back_to_back: host wall time around %d steps, device drained at either end, median of %d "
+                     "(working set 16 B per parameter, cache-resident); cold: one step behind a 512 MiB fill, host wall time to "
+                     "the drained device and the device events around it, median of %d; variants alternate inside every "
+                     "repetition" % (inner, reps, reps),
+           "variants": {k: {"back_to_back_ms": med(warm[k]), "back_to_back_min_ms": min(warm[k]), "cold_wall_ms": med(cold_wall[k]),
+                            "cold_event_ms": med(cold_dev[k]), "cold_event_min_ms": min(cold_dev[k])} for k in variants}}
+    for k in ("fused_adam", "fused_adam_max_grad_norm"):
+        opt = variants[k][1]
+        l0 = opt.launches
+        opt.step()
+        rec["variants"][k]["launches_per_step"] = opt.launches - l0
+    v = rec["variants"]
+    for k in ("fused_adam", "fused_adam_max_grad_norm"):
+        v[k]["cold_GB/s"] = (28.0 + (4.0 if k.endswith("norm") else 0.0)) * n_param / v[k]["cold_event_ms"] / 1e6
+    v["copy_probe_28B_per_param"]["cold_GB/s"] = 28.0 * n_param / v["copy_probe_28B_per_param"]["cold_event_ms"] / 1e6
+    rec["back_to_back_speedup_vs_foreach"] = v["torch_adam_foreach"]["back_to_back_ms"] / v["fused_adam"]["back_to_back_ms"]
+    rec["back_to_back_speedup_vs_torch_fused"] = v["torch_adam_fused"]["back_to_back_ms"] / v["fused_adam"]["back_to_back_ms"]
+    rec["back_to_back_speedup_clipped_vs_foreach_plus_clip"] = (
+        v["torch_adam_foreach_plus_clip_grad_norm"]["back_to_back_ms"] / v["fused_adam_max_grad_norm"]["back_to_back_ms"])
+    _write_case(rec, out_path)
+
+
 test_inputs.__test__ = False  # (a benchmark, not a test)
+if len(sys.argv) > 1 and sys.argv[1] == "optim":
+    optim_step(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "test_inputs":
     test_inputs(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)

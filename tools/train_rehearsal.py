@@ -53,13 +53,19 @@ def main():
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--augment", action="store_true", help="blur and colour-jitter the simulated images (dataset_utils.py:49-83)")
+    ap.add_argument("--optimizer", choices=("torch", "fused"), default="torch",
+                    help="fused: activezero_amd.optim.FusedAdam (K27 / K28) in place of torch.optim.Adam")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     ds = SyntheticMessytableDataset(length=a.iters * a.batch, device=dev, augment=a.augment)
     loader = torch.utils.data.DataLoader(ds, batch_size=a.batch, shuffle=False, num_workers=0)
     torch.manual_seed(1)
     model = PSMNet(MAX_DISP).to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr=2e-4, betas=(0.9, 0.999))
+    if a.optimizer == "fused":
+        from activezero_amd.optim import FusedAdam
+        opt = FusedAdam(model.parameters(), lr=2e-4, betas=(0.9, 0.999))
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=2e-4, betas=(0.9, 0.999))
     for i, sample in enumerate(loader):
         s, r = train_sample(sample, model, opt)
         print(f"iter {i}: sim loss {s:.4f}  real reprojection loss {r:.5f}", flush=True)
