@@ -6,10 +6,12 @@ This module owns how an amax gets to the launch that needs it:
     backward, residual sums, through a pre-zeroed array from ZEROS) and valid while the tensor's version counter stands
     (_set_amax / _get_amax); absmax() takes it with a pass of az_absmax when nobody attached one;
   * weights get theirs once per version -- once per optimizer step -- from the cache behind weight_amax(), which
-    prime_weight_amax() fills for a whole model in one call of az_absmax_multi.
+    prime_weight_amax() fills for a whole model in one call of az_absmax_multi; an entry answers only for the tensor it
+    was taken from (Source: the record every address-keyed table of this library keeps of its sources).
 """
 import os
 import threading
+import weakref
 
 import numpy as np
 import torch
@@ -71,6 +73,13 @@ def check_amax(t, am):
                            "(written through a raw pointer or .data without packing.touched / a fresh amax.absmax?)")
 
 
+def debug_check(t, am):
+    """AZ_DEBUG_AMAX=1: the memoised amax array `am` of the weight t still bounds it (a stale one: t was written through
+    `.data` or a raw pointer without packing.touched)"""
+    if _DEBUG_AMAX:
+        check_amax(t, am)
+
+
 def absmax(t):
     """device scalar max |t| (largest finite magnitude), the operand scale of the f16x3 kernels: taken by the kernel that
     produced t where that is one of this library's (BatchNorm apply / backward, residual sums), by a pass of az_absmax
@@ -86,7 +95,58 @@ def absmax(t):
     return am
 
 
-_W_AMAX = {}  # (data_ptr, version, device, numel) -> (amax array of a weight tensor, the tensor: its address stays its own)
+class Source:
+    """What an address-keyed table of this library remembers of a tensor it made an entry from, so that the entry answers
+    for that tensor alone.  A key of (address, version counter) cannot tell: `p.data = x`, module.to() / .cpu() / .cuda() /
+    .float() and vector_to_parameters replace a parameter's storage WITHOUT moving its counter, the old block is freed, and
+    another tensor -- or the same parameter, two assignments later -- can stand at the old address with the old counter.
+      * the storage the entry was made from is pinned (a detached alias): while the entry lives the allocator cannot hand
+        that address to anybody else;
+      * the tensor itself is kept (weak = True: by weak reference), and a hit is verified (answers): the caller's tensor
+        must lie at the recorded address in the pinned storage, and be the recorded tensor -- which must not have left --
+        or an alias of the same shape whose counter stands where the recorded tensor's does (a detached alias or the
+        gated alias of a training pass: they share the counter).
+    What this cannot see is a write through `.data` or a raw pointer into storage that stays where it is: after one,
+    call packing.touched(*tensors)."""
+    __slots__ = ("_src", "pin", "ptr", "store", "weak")
+
+    def __init__(self, t, weak=False):
+        self.weak = weak
+        base = t._base  # (a whole-tensor view -- the gated alias of a training pass -- stands for the tensor it views:
+        if base is not None and base.data_ptr() == t.data_ptr() and base.shape == t.shape and base.stride() == t.stride():
+            t = base    # the alias would stay behind in the old storage when the parameter's is replaced)
+        self._src = weakref.ref(t) if weak else t
+        self.pin = t.detach()
+        self.ptr, self.store = t.data_ptr(), t.untyped_storage()._cdata
+
+    def stands(self):
+        """the recorded tensor, if it is alive and still where it was; None otherwise"""
+        src = self._src() if self.weak else self._src
+        if src is None or src.data_ptr() != self.ptr or src.untyped_storage()._cdata != self.store:
+            return None
+        return src
+
+    __call__ = stands  # (where a weak reference stood before: "dead" now includes "has left its address")
+
+    def answers(self, t):
+        if t is None or t.data_ptr() != self.ptr or t.untyped_storage()._cdata != self.store:
+            return False
+        src = self.stands()
+        if src is None:
+            return False
+        return src is t or (src._version == t._version and src.shape == t.shape and src.stride() == t.stride())
+
+
+def sources(tensors):
+    return tuple(Source(t) if t is not None else None for t in tensors)
+
+
+def same_sources(srcs, tensors):
+    """every entry of `srcs` (sources(...) at the time of the entry) answers for the tensor at its place"""
+    return len(srcs) == len(tensors) and all((t is None) if s is None else s.answers(t) for s, t in zip(srcs, tensors))
+
+
+_W_AMAX = {}  # (data_ptr, version, device, numel) -> (amax array of a weight tensor, the Source it was taken from)
 _W_LOCK = threading.Lock()
 
 
@@ -99,16 +159,24 @@ def remember_weight_amax(weight, am):
     with _W_LOCK:
         if len(_W_AMAX) > 512:
             _W_AMAX.clear()
-        _W_AMAX[_w_key(weight)] = (am, weight)
+        _W_AMAX[_w_key(weight)] = (am, Source(weight))
+
+
+def _remembered(weight):
+    """the cached amax array of `weight`, None when there is none or the entry under its key was taken from another tensor
+    (call with _W_LOCK held)"""
+    hit = _W_AMAX.get(_w_key(weight))
+    return hit[0] if (hit is not None and hit[1].answers(weight)) else None
 
 
 def weight_amax(weight, w):
     """amax array of the weight tensor `weight` (w: its detached contiguous form), once per version: the forward pack of
     an optimizer step computes it, the input gradient's pack reuses it"""
     with _W_LOCK:
-        hit = _W_AMAX.get(_w_key(weight))
-    if hit is not None:
-        return hit[0]
+        am = _remembered(weight)
+    if am is not None:
+        debug_check(w, am)
+        return am
     am = absmax(w)
     remember_weight_amax(weight, am)
     return am
@@ -151,6 +219,8 @@ class MultiAbsmax:
 
 _PRIME = MultiAbsmax()
 _PRIME_ROWS = {}  # (device index, ((data_ptr, numel), ...)) -> the [len, AMAX_SLOTS] arrays of that set of weights
+# (rows are found by address alone, which is safe because nobody is ANSWERED from them by address: every call rewrites all
+#  rows of its set from the tensors that stand there now, and a row reaches a launch only through _W_AMAX's verified hit)
 
 
 def prime_weight_amax(weights):
@@ -160,7 +230,7 @@ def prime_weight_amax(weights):
     stream order, as the rows of packing.PackPlan are), so that the call's device tables are uploaded once per set."""
     with _W_LOCK:
         todo = [w for w in weights if w is not None and w.is_cuda and w.dtype == torch.float32 and w.numel() > 0
-                and _w_key(w) not in _W_AMAX]
+                and _remembered(w) is None]
         if not todo:
             return
         dets = [w.detach().contiguous() for w in todo]

@@ -22,7 +22,7 @@ import os
 import torch
 
 from . import _lib, conv3d, overlap, packing, profiler
-from .amax import absmax, _get_amax, weight_amax
+from .amax import absmax, debug_check, _get_amax, weight_amax
 from .ops import _call, _chk, _p, _stream
 
 _SAME = {(3, 3, 1), (3, 3, 2), (1, 1, 1), (3, 5, 1)}
@@ -82,7 +82,9 @@ def _pack_f16(weight, cin, cout, ci_real, co_real, s_out, s_in, kh, kw, flip, ca
 
     if cache:
         key = (packing.cache_key(weight), "f16", cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip))
-        return packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
+        hit = packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
+        debug_check(w, hit[1])
+        return hit
     hit = packing.planned_pack(weight, w, packing.PACK_2D_SAME, cin, cout, ci_real, co_real, s_out, s_in, kh * kw, flip, pack_now)
     return hit if hit is not None else make()
 

@@ -19,7 +19,7 @@ import os
 import torch
 
 from . import _lib, overlap, packing, profiler
-from .amax import AMAX_SLOTS, ZEROS, absmax, _get_amax, _set_amax, weight_amax
+from .amax import AMAX_SLOTS, ZEROS, absmax, debug_check, _get_amax, _set_amax, weight_amax
 from .handover import slot_contribute, slot_leftover, slot_register, sum_parts
 from .ops import _call, _chk, _p, _stream
 
@@ -299,7 +299,9 @@ def _pack_f16(weight, op_cin, op_cout, stride_out, stride_in, flip, mode, cache=
 
     if cache:
         key = (packing.cache_key(weight), op_cin, op_cout, stride_out, stride_in, bool(flip), F16X3, mode)
-        return packing.memo(packing.PACK_CACHE, key, make, (weight,), 256)
+        hit = packing.memo(packing.PACK_CACHE, key, make, (weight,), 256)
+        debug_check(w, hit[1])
+        return hit
     kind = _lib.lib().az_conv3d_f16_layout(mode, op_cin, op_cout)
     if kind < 0:
         raise RuntimeError(f"az_conv3d_f16_layout({mode}, {op_cin}, {op_cout}): {kind}")

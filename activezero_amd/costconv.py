@@ -58,12 +58,12 @@ _MERGED_CACHE = {}
 def _merged_kernels(weight, ndisp):
     """(K_L bulk [ncls*32,32,3,3], K_L edge [ncls*128,32,3,3], K_R [ncls*64,32,3,5]) of a [32,64,3,3,3] weight;
     differentiable.  Memoised between no_grad forwards on the weight's version counter."""
-    from .packing import cache_get, cache_put
+    from .packing import Source, cache_get, cache_put
     ncls = num_classes(ndisp)
     key = (weight.data_ptr(), weight._version, weight.device.index, ncls) if not torch.is_grad_enabled() else None
     if key is not None:
         hit = cache_get(_MERGED_CACHE, key)
-        if hit is not None:
+        if hit is not None and hit[3].answers(weight):  # (not the weight that stood at this address before)
             return hit[:3]
     cl = torch.channels_last
     ml, mr = _masks(weight.device, ndisp)
@@ -77,7 +77,7 @@ def _merged_kernels(weight, ndisp):
            kl[:, :4].reshape(ncls * 4 * 32, 32, 3, 3).contiguous(memory_format=cl),
            kr.reshape(ncls * 2 * 32, 32, 3, 5).contiguous(memory_format=cl))
     if key is not None:
-        cache_put(_MERGED_CACHE, key, out + (weight,), 16)  # (keeps the source alive: its address stays unique)
+        cache_put(_MERGED_CACHE, key, out + (Source(weight),), 16)  # (the source: a hit is verified against it)
     return out
 
 

@@ -139,7 +139,7 @@ def _pack_bf16(weights, cache):
         _call("az_conv2d_pack_weights_bf16", _p(packed), _p(w), cin, cout, cin * kh * kw, kh * kw, kh, kw, _stream())
         return packed
 
-    return memo(_PACK_CACHE, cache_key(*weights) if cache else None, make, (weights,), 64)
+    return memo(_PACK_CACHE, cache_key(*weights) if cache else None, make, tuple(weights), 64)
 
 
 def conv3x3_bf16(xr, packed, cin, cout, bias=None, residual=None, act=ACT_NONE, gate_z=None, gate_h=None, h1=False,
@@ -173,7 +173,7 @@ def _pack_h1(weights, flipped, cache=True):
             _call("az_conv2d_pack_weights_h1", _p(packed), _p(w), None, cin, cout, cin * 9, 9, 0, _stream())
         return packed
 
-    return memo(_PACK_CACHE, ("h1", bool(flipped)) + cache_key(*weights) if cache else None, make, (weights,), 64)
+    return memo(_PACK_CACHE, ("h1", bool(flipped)) + cache_key(*weights) if cache else None, make, tuple(weights), 64)
 
 
 def _rows(t):
@@ -231,7 +231,7 @@ def _pack_bf16_flipped(weights, cache):
         _call("az_conv2d_pack_weights_bf16_flipped", _p(packed), _p(w), cout, cin, 9, cin * 9, 3, 3, _stream())
         return packed
 
-    return memo(_PACK_CACHE, ("flip",) + cache_key(*weights) if cache else None, make, (weights,), 64)
+    return memo(_PACK_CACHE, ("flip",) + cache_key(*weights) if cache else None, make, tuple(weights), 64)
 
 
 class _GRUStepBf16(torch.autograd.Function):

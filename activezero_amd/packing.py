@@ -23,15 +23,24 @@ from .ops import _call, _p, _stream
 # Function.  Keys hold the tensors' storage address AND version counter, so an optimizer step or a
 # load_state_dict (both write in place) invalidates them; a BatchNorm's key also holds
 # num_batches_tracked, because this library's own train kernels update running_mean / running_var
-# through raw pointers, which no version counter sees.  Each entry keeps its source tensors alive, so
-# their addresses cannot be recycled for other data.  A lock makes the dicts safe under the threads of
-# nn.DataParallel (train.py:540-541).
+# through raw pointers and then bump the counters themselves (touched()).
+# What a key does NOT say is whose (address, counter) it is: `p.data = t`, module.to() / .cpu() / .cuda() / .float()
+# and vector_to_parameters replace a parameter's storage without moving its counter, and another tensor with an
+# equal counter -- or the same parameter, later -- can stand at the old address.  So each entry records its sources
+# (amax.Source): the storage it was packed from stays pinned while the entry lives, and every hit is verified --
+# the recorded tensor must still stand where it was packed, and the caller's tensor must be it or an alias of it
+# (detached, or the gated alias of a training pass).  What nothing here can see is a write through `.data` or a raw
+# pointer into storage that stays where it is: after one, call touched(*tensors).
+# A lock makes the dicts safe under the threads of nn.DataParallel (train.py:540-541).
 PACK_CACHE, AFFINE_CACHE = {}, {}
 CACHE_LOCK = threading.Lock()
 
 
 def cache_key(*tensors):
     return tuple((t.data_ptr(), t._version, t.device.index) for t in tensors if t is not None)
+
+
+Source, sources, same_sources = amax.Source, amax.sources, amax.same_sources  # (the rule of every address-keyed table, stated once)
 
 
 def cache_get(cache, key):
@@ -48,14 +57,16 @@ def cache_put(cache, key, value, limit):
 
 def memo(cache, key, make, keep, limit):
     """make()'s value, remembered in `cache` under `key` (None: not memoised, the call site has autograd on) together with
-    the source tensors `keep`; a cache that has grown past `limit` entries is emptied"""
+    the source tensors `keep` the key was taken from; a hit answers only for those tensors (same_sources); a cache that has
+    grown past `limit` entries is emptied"""
     if key is None:
         return make()
+    keep = tuple(keep)
     hit = cache_get(cache, key)
-    if hit is not None:
+    if hit is not None and same_sources(hit[1], keep):
         return hit[0]
     value = make()
-    cache_put(cache, key, (value,) + tuple(keep), limit)
+    cache_put(cache, key, (value, sources(keep)), limit)
     return value
 
 
@@ -75,7 +86,10 @@ def touched(*tensors):
 #     and the next step's prepack is enqueued behind them on the same stream;
 #   * only tensors registered through prepack() -- live nn.Parameters, held by weak reference -- have entries: derived
 #     weights (the merged kernels of K3', DataParallel replicas) change address every step and keep the per-call route;
-#   * an entry is valid for one (address, version counter): optimizer steps and load_state_dict write in place and bump it.
+#   * an entry is valid for one (address, version counter): optimizer steps and load_state_dict write in place and bump it;
+#   * an address belongs to the registered parameter only while that parameter stands there: once its storage has been
+#     replaced (`p.data = t`, module.to(), vector_to_parameters) the plan answers for nobody at the old address, and the
+#     next prepack drops what it held for it.
 PACK_2D_SAME, PACK_2D_ROLL, PACK_3D_GATHER, PACK_3D_ROLL, PACK_3D_ROLL2 = (
     CONST["AZ_PACK_" + k] for k in ("2D_SAME", "2D_ROLL", "3D_GATHER", "3D_ROLL", "3D_ROLL2"))
 _PLAN_ON = os.environ.get("AZ_PACK_PLAN", "1") != "0"  # (read once) 0: every image packed by its own launch, as in round 4
@@ -110,9 +124,9 @@ class PackPlan:
     def __init__(self, device):
         self.device = device
         self.lock = threading.RLock()
-        self.registered = {}   # data_ptr -> weakref of the parameter
+        self.registered = {}   # data_ptr -> weak amax.Source of the parameter: it and the storage it was registered with
         self.entries = {}      # (data_ptr, kind, cin, cout, ci_real, co_real, s_co, s_ci, taps, flip) -> _PackEntry
-        self.amax_rows = {}    # data_ptr -> (row tensor [AMAX_SLOTS], weakref)
+        self.amax_rows = {}    # data_ptr -> (row tensor [AMAX_SLOTS], the parameter's Source)
         self.amax_blocks = []  # [tensor [256, AMAX_SLOTS], next row]
         self.table = None      # (descs, block_desc, first_block, nd, nblocks, entry list) on the device: the last one used
         self.tables = {}       # tuple of registered addresses -> table + the amax pointers it was built with
@@ -123,7 +137,7 @@ class PackPlan:
     def amax_row(self, w):
         ptr = w.data_ptr()
         hit = self.amax_rows.get(ptr)
-        if hit is not None and hit[1]() is not None:
+        if hit is not None and hit[1]() is w:  # (the row of this parameter, not of one that stood here before it)
             return hit[0]
         if not self.amax_blocks or self.amax_blocks[-1][1] >= self.amax_blocks[-1][0].shape[0]:
             self.amax_blocks.append([torch.zeros(256, AMAX_SLOTS, dtype=torch.float32, device=self.device), 0])
@@ -132,12 +146,20 @@ class PackPlan:
         blk[1] += 1
         return row
 
-    def alive(self, ptr):
+    def owner(self, ptr):
+        """the registered parameter that stands at this address; None once it has died or its storage was replaced
+        (`p.data = t`, module.to(), vector_to_parameters: the address is then free for another tensor)"""
         r = self.registered.get(ptr)
-        return r is not None and r() is not None
+        return r() if r is not None else None
+
+    def owns(self, weight):
+        """the registered parameter `weight` is -- itself or an alias over its storage with its version counter's value
+        (detached, or the gated alias of a training pass) -- or None"""
+        r = self.registered.get(weight.data_ptr())
+        return r() if (r is not None and r.answers(weight)) else None
 
     def purge(self):
-        dead = [p for p, r in self.registered.items() if r() is None]
+        dead = [p for p in self.registered if self.owner(p) is None]
         if dead:
             dead = set(dead)
             for p in dead:
@@ -153,10 +175,12 @@ class PackPlan:
         buffer already holds the image of the parameter's current version; None for unregistered tensors"""
         ptr = weight.data_ptr()
         with self.lock:
-            if not self.alive(ptr):
+            if self.owns(weight) is None:
                 return None, False
             key = (ptr, kind, cin, cout, ci_real, co_real, int(s_co), int(s_ci), taps, bool(flip))
             e = self.entries.get(key)
+            if e is not None and e.wref is not self.registered[ptr]:
+                e = None  # (an image of the parameter that stood at this address before: never served, replaced below)
             if e is None:
                 e = _PackEntry()
                 e.wref, e.kind, e.cin, e.cout, e.ci_real, e.co_real = self.registered[ptr], kind, cin, cout, ci_real, co_real
@@ -177,24 +201,29 @@ class PackPlan:
         self.table = (torch.from_numpy(descs.view(np.uint8)).to(dev), torch.from_numpy(block_desc).to(dev),
                       torch.from_numpy(first).to(dev), len(todo), nblocks, list(todo))
 
+    def register(self, w):
+        """the address of parameter `w` is its own from now on, for as long as it stands there"""
+        with self.lock:
+            r = self.registered.get(w.data_ptr())
+            if r is None or r() is not w:
+                self.registered[w.data_ptr()] = Source(w, weak=True)
+
     def prepack(self, weights):
         """register `weights` (nn.Parameters) and bring every recorded image of THEIRS up to their current version in one
         launch (a table per set of weights: another live model's images are not this call's business); the amax arrays of
         all of them in one call of az_absmax_multi (as prime_weight_amax)"""
         with self.lock:
             self.purge()
-            import weakref
             mine = []
             for w in weights:
                 if w is None or not w.is_cuda or w.dtype != torch.float32 or w.device != self.device:
                     continue
-                r = self.registered.get(w.data_ptr())
-                if r is None or r() is not w:
-                    self.registered[w.data_ptr()] = weakref.ref(w)
+                self.register(w)
                 mine.append(w.data_ptr())
             setkey = tuple(sorted(set(mine)))
             owned = set(setkey)
-            todo = [e for k, e in self.entries.items() if k[0] in owned and e.wref() is not None]
+            todo = [e for k, e in self.entries.items()  # (the images of the parameters that stand there NOW)
+                    if k[0] in owned and e.wref is self.registered[k[0]] and e.wref() is not None]
             stale = [e for e in todo if e.version != e.wref()._version]
             if not stale:
                 return
