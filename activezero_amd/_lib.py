@@ -108,6 +108,7 @@ with open(HEADER) as _f:
     _SIGS, _RESTYPE, CONST, _STRUCTS = parse_header(_f.read())
 PACK_DESC, UNPACK_DESC, ABSMAX_DESC = _STRUCTS["AzPackDesc"], _STRUCTS["AzUnpackDesc"], _STRUCTS["AzAbsmaxDesc"]
 ADAM_DESC = _STRUCTS["AzAdamDesc"]
+MS_LOSS_DESC = _STRUCTS["AzMsLossDesc"]
 
 
 def declared_symbols():

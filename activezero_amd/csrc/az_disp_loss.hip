@@ -9,6 +9,7 @@
 #include "az_block_reduce.h"
 #include "az_common.h"
 #include "az_disp_terms.h"
+#include "az_smooth_l1.h"  // dl_clamp1 (shared with K29)
 
 #define DL_BLOCK 256
 
@@ -37,9 +38,6 @@ disp_loss_fwd_kernel(double *__restrict__ acc, const float *__restrict__ p3, con
     }
     dl_flush<4>(v, acc);
 }
-
-// clamp(d, -1, 1) that keeps a NaN, as the autograd gradient of smooth-L1 does (fminf / fmaxf would give -1)
-__device__ __forceinline__ float dl_clamp1(float d) { return az_min_nan(az_max_nan(d, -1.f), 1.f); }
 
 // d loss / d pred_k = w_k * gloss / count * clamp(pred_k - gt, -1, 1) on valid pixels, 0 elsewhere
 __global__ void __launch_bounds__(DL_BLOCK)

@@ -6,6 +6,7 @@ All wrappers validate like the reference does (contiguity / dtype / device /
 sign, utils/warp_ops.py:69-77) and raise on violation -- there is no eager or
 CPU fallback.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -292,6 +293,89 @@ def disp_loss(pred3, pred2, pred1, gt, mask=None, lo=0.0, hi=float("inf")):
     """smooth_l1(pred3) + 0.7 smooth_l1(pred2) + 0.5 smooth_l1(pred1), each a mean over the valid
     pixels: `mask` (bool/uint8, same shape) or, when mask is None, lo < gt < hi.  One pass, no sync."""
     return _DispLoss.apply(pred3, pred2, pred1, gt, mask, lo, hi)
+
+
+# ----------------------------------------------------------------------------
+# K29 multi-scale disparity loss (dispnet_disp, default_disp)
+# ----------------------------------------------------------------------------
+MS_LOSS_MAX = _lib.CONST["AZ_MS_LOSS_MAX"]
+
+
+def _ms_descs(ps, grads, shifts):
+    """the AzMsLossDesc table of one call, in host memory (the library copies it into the kernel arguments)"""
+    descs = np.zeros(len(ps), dtype=_lib.MS_LOSS_DESC)
+    for k, (p, g, s) in enumerate(zip(ps, grads, shifts)):
+        descs[k] = (p.data_ptr(), 0 if g is None else g.data_ptr(), s, p.shape[2], p.shape[3], 0)
+    return descs
+
+
+class _MsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gt, mask, shifts, weights, lo, hi, *preds):
+        gt = _chk(gt.contiguous(), "disp_gt")
+        if gt.dim() != 4 or gt.shape[1] != 1:
+            raise RuntimeError(f"disp_gt: expected [B,1,H,W], got {tuple(gt.shape)}")
+        m = _mask_u8(mask, gt)
+        b, _, h, w = gt.shape
+        ps = []
+        for k, (p, s) in enumerate(zip(preds, shifts)):
+            p = _chk(p.contiguous(), f"preds[{k}]")
+            if (h >> s) < 1 or (w >> s) < 1:
+                raise RuntimeError(f"preds[{k}]: a {h}x{w} map has no pixels at scale 1/{1 << s}")
+            if tuple(p.shape) != (b, 1, h >> s, w >> s):
+                raise RuntimeError(f"preds[{k}]: shape {tuple(p.shape)} != {(b, 1, h >> s, w >> s)} (scale 1/{1 << s})")
+            ps.append(p)
+        n = len(ps)
+        acc = torch.zeros(n, 2, dtype=torch.float64, device=gt.device)
+        descs = _ms_descs(ps, [None] * n, shifts)
+        with torch.cuda.device(gt.device):
+            _call("az_ms_loss_fwd", _p(acc), descs.ctypes.data, n, _p(gt), _p(m), float(lo), float(hi), b, h, w, _stream())
+        # python-float weights: kernel arguments, no blocking copy.  0/0 = nan, as the reference's empty mean
+        means = acc[:, 0] / acc[:, 1]
+        loss = means[0] * weights[0]
+        for k in range(1, n):
+            loss = torch.add(loss, means[k], alpha=weights[k])
+        ctx.save_for_backward(gt, m if m is not None else gt.new_empty(0), acc, *ps)
+        ctx.has_mask, ctx.lo, ctx.hi, ctx.shifts, ctx.weights = m is not None, float(lo), float(hi), shifts, weights
+        means = means.to(torch.float32)
+        ctx.mark_non_differentiable(means)
+        return loss.to(torch.float32), means
+
+    @staticmethod
+    def backward(ctx, gloss, _gmeans):
+        gt, m, acc, *ps = ctx.saved_tensors
+        gloss = _chk(gloss.contiguous().to(torch.float32).reshape(1), "grad_loss")
+        grads = [torch.empty_like(p) if need else None for p, need in zip(ps, ctx.needs_input_grad[6:])]
+        descs = _ms_descs(ps, grads, ctx.shifts)
+        wts = np.asarray(ctx.weights, dtype=np.float32)
+        b, _, h, w = gt.shape
+        with torch.cuda.device(gt.device):
+            _call("az_ms_loss_bwd", descs.ctypes.data, wts.ctypes.data, len(ps), _p(gt), _p(m) if ctx.has_mask else None,
+                  ctx.lo, ctx.hi, _p(gloss), _p(acc), b, h, w, _stream())
+        return (None,) * 6 + tuple(grads)
+
+
+def multiscale_disp_loss(preds, gt, mask=None, shifts=None, weights=None, lo=0.0, hi=float("inf")):
+    """sum_k weights[k] * mean of smooth_l1(preds[k] - gt at stride 2^shifts[k]) over the valid pixels of scale k.
+    gt [B,1,H,W]; preds[k] [B,1,H >> shifts[k], W >> shifts[k]], its pixel (y, x) is compared with gt at
+    (y << shifts[k], x << shifts[k]) -- F.interpolate(scale_factor=1 / 2^s), nearest.  Valid: `mask` (bool / uint8, gt's shape)
+    at that pixel, or, when mask is None, lo < gt < hi.  shifts default to 0 (every prediction at full resolution), weights
+    to 1; at most MS_LOSS_MAX predictions.  One autograd node, one forward and one backward launch, no boolean indexing and
+    no host sync.  Returns the fp32 scalar; its attribute `scale_means` is the fp32 device tensor [len(preds)] of the
+    per-scale means (nan for a scale without valid pixels, as the reference's empty mean), for logging without a sync."""
+    preds = list(preds)
+    n = len(preds)
+    if not 1 <= n <= MS_LOSS_MAX:
+        raise RuntimeError(f"multiscale_disp_loss takes 1..{MS_LOSS_MAX} predictions, got {n}")
+    shifts = (0,) * n if shifts is None else tuple(int(s) for s in shifts)
+    weights = (1.0,) * n if weights is None else tuple(float(x) for x in weights)
+    if len(shifts) != n or len(weights) != n:
+        raise RuntimeError(f"{n} predictions, {len(shifts)} shifts, {len(weights)} weights")
+    if any(not 0 <= s <= 30 for s in shifts):
+        raise RuntimeError(f"shifts must be in 0..30, got {shifts}")
+    loss, means = _MsLoss.apply(gt, mask, shifts, weights, lo, hi, *preds)
+    loss.scale_means = means
+    return loss
 
 
 def disp_metrics(disp_gt, depth_gt, disp_pred, mask, focal_x_baseline=None, depth_pred=None):

@@ -22,3 +22,31 @@ def psmnet_disp_range(pred_disp, disp_gt_l, max_disp, min_disp=0.0):
     so the caller builds no mask tensor at all."""
     pred3, pred2, pred1 = pred_disp
     return ops.disp_loss(pred3, pred2, pred1, disp_gt_l, None, float(min_disp), float(max_disp))
+
+
+DISPNET_WEIGHTS = (1.0, 1.0, 1.0, 0.8, 0.6, 0.4, 0.2)  # utils/losses.py:18, scale 1/2^k for prediction k
+
+
+def dispnet_disp(disp_ests, disp_gt, mask):
+    """sum_k w_k * SL1 mean of disp_ests[k] ([B,1,H >> k,W >> k]) against disp_gt and mask ([B,1,H,W], bool) read at
+    stride 2^k -- what the reference's F.interpolate(scale_factor=1 / 2^k) of both picks.  One K29 launch for the seven
+    scales; `.scale_means` of the result holds the per-scale means on the device."""
+    n = len(disp_ests)
+    return ops.multiscale_disp_loss(disp_ests, disp_gt, mask, shifts=range(n), weights=DISPNET_WEIGHTS[:n])
+
+
+def dispnet_disp_range(disp_ests, disp_gt, max_disp, min_disp=0.0):
+    """dispnet_disp with the mask rule min_disp < gt < max_disp applied in the kernel at the strided pixel."""
+    n = len(disp_ests)
+    return ops.multiscale_disp_loss(disp_ests, disp_gt, None, shifts=range(n), weights=DISPNET_WEIGHTS[:n],
+                                    lo=float(min_disp), hi=float(max_disp))
+
+
+def default_disp(pred_disp, disp_gt_l, mask):
+    """F.smooth_l1_loss(pred_disp[mask], disp_gt_l[mask]) (utils/losses.py:71-72: every validation step), all [B,1,H,W]."""
+    return ops.multiscale_disp_loss([pred_disp], disp_gt_l, mask)
+
+
+def default_disp_range(pred_disp, disp_gt_l, max_disp, min_disp=0.0):
+    """default_disp with the mask rule min_disp < gt < max_disp applied in the kernel."""
+    return ops.multiscale_disp_loss([pred_disp], disp_gt_l, None, lo=float(min_disp), hi=float(max_disp))

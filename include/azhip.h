@@ -827,6 +827,33 @@ int az_disp_metrics(double *acc8, const float *disp_gt, const float *depth_gt,
                     const float *disp_pred, const float *depth_pred, const float *focal_x_baseline,
                     const unsigned char *mask, int B, long long per_batch, void *stream);
 
+/* ---- K29: multi-scale masked smooth-L1 disparity loss (az_ms_loss.hip) ------------------------------------------
+ * Replaces utils/losses.py:17-32 dispnet_disp (per scale two F.interpolate calls, two casts, two boolean-index compactions
+ * and a smooth_l1 mean) and utils/losses.py:71-72 default_disp (nd = 1, shift = 0).  gt [B,1,H,W] f32; `mask` one byte per
+ * full-resolution pixel, or NULL for the range rule lo < gt < hi (a NaN gt is invalid), as for K12.  Prediction k is
+ * [B,1,h_k,w_k] f32 with h_k = H >> shift_k, w_k = W >> shift_k, and its pixel (b,y,x) is compared with the full-resolution
+ * pixel (b, y << shift_k, x << shift_k) -- what F.interpolate(scale_factor = 1 / 2^shift_k), nearest, reads.  With
+ * SL1(d) = 0.5 d^2 for |d| < 1 and |d| - 0.5 otherwise:
+ *   loss = sum_k w_k * mean over {(b,y,x): valid(b, y << shift_k, x << shift_k)} of
+ *          SL1(pred_k[b,0,y,x] - gt[b,0,y << shift_k,x << shift_k])
+ * descs (and weights) are nd entries in HOST memory, read before the call returns and passed on in the kernel arguments:
+ * no upload, no synchronisation.  One launch per call whatever nd is.
+ * A required pointer null: AZ_ENULL; nd outside 1..AZ_MS_LOSS_MAX, shift outside 0..30, h_k != H >> shift_k,
+ * w_k != W >> shift_k or either < 1 (the reference raises on a zero-sized scale): AZ_EINVAL -- all before any launch. */
+#define AZ_MS_LOSS_MAX 8
+typedef struct AzMsLossDesc {
+    const float *pred;
+    float *grad; /* az_ms_loss_bwd only; NULL: this prediction needs no gradient, nothing is written for it */
+    int shift, h, w, reserved;
+} AzMsLossDesc;
+/* acc (caller-zeroed fp64, 2 nd entries): acc[2k] += sum SL1 over prediction k's valid pixels, acc[2k+1] += their count */
+int az_ms_loss_fwd(double *acc, const AzMsLossDesc *descs, int nd, const float *gt, const unsigned char *mask, float lo,
+                   float hi, int B, int H, int W, void *stream);
+/* grad_k = (weights[k] * (gloss[0] / (float)acc[2k+1])) * clamp(pred_k - gt, -1, 1) on valid pixels (the clamp keeps a NaN),
+ * 0 elsewhere -- selected, not multiplied: a scale without valid pixels gets zeros.  Fully written, no pre-zeroing. */
+int az_ms_loss_bwd(const AzMsLossDesc *descs, const float *weights, int nd, const float *gt, const unsigned char *mask,
+                   float lo, float hi, const float *gloss, const double *acc, int B, int H, int W, void *stream);
+
 /* ---- K22: the metrics of a test batch per image and per object label, one pass (az_obj_metrics.hip) ------------
  * replaces utils/cascade_metrics.py:65-126 compute_obj_err -- label.unique().tolist() (a host sync), then per object a
  * (label == obj) & mask temporary and a chain of masked reductions over the whole map -- and gives compute_err_metric per

@@ -46,7 +46,13 @@ times the optimizer step on the full-size PSMNet parameter set (maxdisp 192) wit
 its default (foreach) and fused=True forms, activezero_amd.optim.FusedAdam (K28) without and with max_grad_norm=1.0 (K27), and
 foreach Adam behind clip_grad_norm_, beside the copy probe moving the update's 28 B per parameter; back to back (the 80 MB of
 p, g, m, v stay in the 256 MiB cache) and behind a 512 MiB fill (they arrive from HBM, as in a training step);
-profiles/optim_step.json.  Recorded, not gated."""
+profiles/optim_step.json.  Recorded, not gated.
+
+    python tools/bench_aux_kernels.py ms_loss [out.json]
+times the multi-scale disparity loss (K29) forward + backward at B = 4, 256x512 and 544x960, as dispnet_disp (seven scales) and
+as default_disp (one): the fused autograd node against the same formula written as the torch operator chain (F.interpolate,
+casts, boolean indexing, smooth_l1_loss), with the device kernels and host syncs of one step of each, and the two kernels
+alone against the copy probe moving the bytes they touch; profiles/ms_loss.json.  Recorded, not gated."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -1045,7 +1051,139 @@ def optim_step(out_path=None):
     _write_case(rec, out_path)
 
 
+def ms_loss(out_path=None):
+    import json
+    import statistics
+    import warnings
+    import numpy as np
+    import torch.nn.functional as F
+    import bench as _bench
+    from activezero_amd import ops
+    from activezero_amd.utils import disp_losses
+    dev = torch.device("cuda:0")
+    reps = 30
+    g = torch.Generator(device=dev).manual_seed(0)
+    weights = disp_losses.DISPNET_WEIGHTS
+    probe = _bench.hbm_probe(dev)["GB/s"]
+    doc = {"case": "ms_loss", "copy_probe_GB/s": probe,
+           "timing": "forward + backward of one loss per HIP event pair on the launch stream (host gaps and syncs of the "
+                     "chain included: the stream idles while the host waits), median of %d after 3 warm-up steps; "
+                     "kernels_only: az_ms_loss_fwd + az_ms_loss_bwd through the C ABI, 20 pairs per event pair; device "
+                     "kernels counted by torch.profiler over one step, host syncs by set_sync_debug_mode('warn')" % reps}
+
+    def chain_dispnet(ps, gt, mask):  # the formula of utils/losses.py:17-32 as the torch operator chain
+        total = 0.0
+        for s, (p, w) in enumerate(zip(ps, weights)):
+            if s:
+                dgt = F.interpolate(gt, scale_factor=1 / (2 ** s))
+                m = F.interpolate(mask.float(), scale_factor=1 / (2 ** s)).bool()
+            else:
+                dgt, m = gt, mask
+            total = total + w * F.smooth_l1_loss(p[m], dgt[m], reduction="mean")
+        return total
+
+    def chain_default(ps, gt, mask):  # utils/losses.py:71-72
+        return F.smooth_l1_loss(ps[0][mask], gt[mask], reduction="mean")
+
+    def step(fn, ps, gt, mask):
+        for p in ps:
+            p.grad = None
+        fn(ps, gt, mask).backward()
+
+    def events(fn, inner=1):
+        for _ in range(3):
+            fn()
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(inner):
+                fn()
+            b.record(); torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b) / inner)
+        return statistics.median(ms), min(ms)
+
+    def count(fn):
+        """(device kernels of one step or None when the profiler is unavailable, launches per K29 kernel, host syncs)"""
+        torch.cuda.synchronize()
+        torch.cuda.set_sync_debug_mode("warn")
+        try:
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                fn()
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
+        syncs = sum("synchroniz" in str(c.message).lower() and "prototype" not in str(c.message).lower() for c in caught)
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                fn()
+                torch.cuda.synchronize()
+            names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower()
+                     and "memset" not in e.name.lower()]
+            return len(names), {n.split("(")[0]: names.count(n) for n in sorted(set(names)) if "ms_loss" in n}, syncs
+        except Exception as err:  # recorded, not hidden
+            return None, {"profiler unavailable: %r" % (err,): 0}, syncs
+
+    for H, W in ((256, 512), (544, 960)):
+        B = 4
+        gt = 2.0 + 90.0 * torch.rand(B, 1, H, W, device=dev, generator=g)
+        gt[:, :, : H // 8] = 0.0
+        mask = (gt > 0) & (gt < 64.0)
+        for name, nd, fused, chain in (("dispnet_disp", 7, lambda ps, a, m: disp_losses.dispnet_disp(ps, a, m), chain_dispnet),
+                                       ("default_disp", 1, lambda ps, a, m: disp_losses.default_disp(ps[0], a, m), chain_default)):
+            ps = [(gt[:, :, ::1 << s, ::1 << s][:, :, :H >> s, :W >> s] + torch.randn(B, 1, H >> s, W >> s, device=dev, generator=g))
+                  .contiguous().requires_grad_() for s in range(nd)]
+            lf, lc = fused(ps, gt, mask), chain(ps, gt, mask)
+            lf, lc = float(lf.detach()), float(lc.detach())
+            assert abs(lf - lc) <= 1e-5 * abs(lc), (name, lf, lc)
+            fm, flo = events(lambda: step(fused, ps, gt, mask))
+            cm, clo = events(lambda: step(chain, ps, gt, mask))
+            fk, fnames, fsync = count(lambda: step(fused, ps, gt, mask))
+            ck, _, csync = count(lambda: step(chain, ps, gt, mask))
+            # the two kernels alone, through the C ABI
+            det = [p.detach() for p in ps]
+            grads = [torch.empty_like(p) for p in det]
+            acc = torch.zeros(nd, 2, dtype=torch.float64, device=dev)
+            gloss = torch.ones(1, device=dev)
+            m8 = mask.view(torch.uint8)
+            d_f = ops._ms_descs(det, [None] * nd, range(nd))
+            d_b = ops._ms_descs(det, grads, range(nd))
+            wts = np.asarray(weights[:nd], dtype=np.float32)
+
+            def pair():
+                ops._call("az_ms_loss_fwd", acc.data_ptr(), d_f.ctypes.data, nd, gt.data_ptr(), m8.data_ptr(), 0.0, float("inf"),
+                          B, H, W, ops._stream())
+                ops._call("az_ms_loss_bwd", d_b.ctypes.data, wts.ctypes.data, nd, gt.data_ptr(), m8.data_ptr(), 0.0, float("inf"),
+                          gloss.data_ptr(), acc.data_ptr(), B, H, W, ops._stream())
+
+            km, klo = events(pair, inner=20)
+            npix = sum(p.numel() for p in det)
+            # per prediction pixel: forward 4 B read, backward 4 B read + 4 B written; gt (4 B) and mask (1 B) once per pass
+            # at scale 0, by touched 64 B lines at the coarser scales (stride >= 16 floats: one line per pixel)
+            gt_lines = sum(min(det[s].numel() * 64, gt.numel() * 4) if s else gt.numel() * 4 for s in range(nd))
+            nbytes = 12.0 * npix + 2.0 * (gt_lines + gt.numel())
+            nf = int(nbytes) // 8
+            src, dst = torch.empty(nf, device=dev).normal_(), torch.empty(nf, device=dev)
+            pm, plo = events(lambda: ops._call("az_hbm_copy_probe", dst.data_ptr(), src.data_ptr(), nf, ops._stream()), inner=20)
+            doc["%s_%dx%d" % (name, H, W)] = {
+                "batch": B, "predictions": nd, "prediction_pixels": npix,
+                "fused_fwd_bwd_ms": fm, "fused_min_ms": flo, "chain_fwd_bwd_ms": cm, "chain_min_ms": clo, "speedup_vs_chain": cm / fm,
+                "fused_device_kernels": fk, "fused_ms_loss_kernels": fnames, "fused_host_syncs": fsync,
+                "chain_device_kernels": ck, "chain_host_syncs": csync,
+                "kernels_only_fwd_plus_bwd_ms": km, "kernels_only_min_ms": klo, "touched_MB": nbytes / 1e6,
+                "kernels_only_GB/s": nbytes / km / 1e6, "copy_probe_ms_same_bytes": pm, "copy_probe_min_ms": plo,
+                "of_copy_probe": pm / km}
+    print(json.dumps(doc))
+    if out_path:
+        with open(out_path, "w") as fh:
+            fh.write(json.dumps(doc, indent=1) + "\n")
+
+
 test_inputs.__test__ = False  # (a benchmark, not a test)
+if len(sys.argv) > 1 and sys.argv[1] == "ms_loss":
+    ms_loss(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "optim":
     optim_step(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
