@@ -88,6 +88,8 @@ def absmax(t):
     if am is not None and _DEBUG_AMAX:
         check_amax(t, am)
     if am is None:
+        if not t.is_contiguous():  # (the kernel reads t.numel() floats from its pointer)
+            raise RuntimeError("absmax: the tensor must be contiguous")
         am = t.new_empty(AMAX_SLOTS)
         with profiler.scope("absmax", bytes=4.0 * t.numel(), bound="hbm"):
             _call("az_absmax", _p(am), _p(t), t.numel(), _stream())

@@ -52,7 +52,7 @@ class _BNAct(torch.autograd.Function):
         nvox = (n // groups) * h * w
         training = bn.training or not bn.track_running_stats
         eps = float(bn.eps)
-        g_, b_ = gamma.detach(), beta.detach()
+        g_, b_ = _chk(gamma, "gamma").detach(), _chk(beta, "beta").detach()  # (read through their pointers)
         lib = _lib.lib()
         with torch.cuda.device(x.device):
             if not training:  # running statistics: one affine map for the whole batch

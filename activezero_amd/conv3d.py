@@ -201,6 +201,8 @@ def eval_affine(bn, like, cache=False):
     src = (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
 
     def make():
+        for t, name in zip(src[:4], ("weight", "bias", "running_mean", "running_var")):
+            _chk(t, "BatchNorm " + name)
         scale, shift = like.new_empty(c), like.new_empty(c)
         _call("az_bn3d_eval_affine", _p(scale), _p(shift), _p(bn.weight.detach()), _p(bn.bias.detach()),
               _p(bn.running_mean), _p(bn.running_var), float(bn.eps), c, _stream())
@@ -461,6 +463,7 @@ class _ConvBN(torch.autograd.Function):
         x = _chk(x, "x")  # (LazyCostVolume never reaches autograd: see conv_bn)
         if residual is not None:
             residual = _chk(residual, "residual")
+        _chk(gamma, "gamma"), _chk(beta, "beta")  # (read through their pointers: a strided view of a parameter is refused)
         training = bn.training or not bn.track_running_stats
         eps = float(bn.eps)
         cin, cout = _fwd_launch(weight, mode)[:2]

@@ -49,8 +49,11 @@ def slot_register(t):
 def sum_parts(parts):
     while len(parts) > 1:
         take, parts = parts[:4], parts[4:]
-        out = torch.empty_like(take[0])
-        ptrs = [_p(_chk(t.contiguous(), "grad")) for t in take] + [None] * (4 - len(take))
+        take = [_chk(t.contiguous(), "grad") for t in take]
+        if any(t.shape != take[0].shape for t in take):
+            raise RuntimeError(f"sum_parts: shapes differ, {[tuple(t.shape) for t in take]}")
+        out = torch.empty_like(take[0])  # (of the contiguous copy: az_sum4 writes linearly, a part may arrive in any format)
+        ptrs = [_p(t) for t in take] + [None] * (4 - len(take))
         _call("az_sum4", _p(out), ptrs[0], ptrs[1], ptrs[2], ptrs[3], out.numel(), _stream())
         parts = [out] + parts
     return parts[0]

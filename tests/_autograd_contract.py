@@ -14,6 +14,9 @@ which this module evaluates on the CPU in fp64 and in fp32.  These checks run on
     check_replay    autograd.grad(retain_graph=True) twice, .backward() twice into .grad,         (state that outlives one
                     then the node's module-level state must be clean                               backward pass)
     check_pruned_then_full   one backward over a pruned graph, then a full one over the same graph and over a new one
+    check_input_forms   the same INPUT values in the other memory format, with the last two dimensions swapped      (strides, storage
+                    in memory, as a slice of a larger NaN-filled buffer, and as contiguous views at storage         offsets and alignment
+                    offsets 12 and 1: each input alone in each form, then all in `format`, all in `offset1`         of the inputs)
 
 Comparison rules (none is fitted to what the code under test returns):
 
@@ -105,12 +108,19 @@ class Node:
     vjp(inputs, cotangents) -> {name: fp64 gradient}: a node that is SPECIFIED to round its operands (the ConvGRU's one-part
     fp16 / bf16 convolutions) cannot be compared with the autograd of its unrounded formula; `vjp` is its chained fp64
     reference with that rounding IN the reference (tests/_gru_fp64ref.py's pieces).  It stands for both evaluations, so
-    e_ref = 0 and the per-tensor rule is its floor, 2e-4."""
+    e_ref = 0 and the per-tensor rule is its floor, 2e-4.
+    refuses: {input name: forms} -- the wrapper REFUSES that input in those memory forms (a `_chk` without `.contiguous()`):
+    check_input_forms then asks for a RuntimeError, and a refusal is a pass.  "*" names every tensor input.
+    unaligned: the documented route that the node takes for a pointer that is not 16-byte aligned (a sentence naming the
+    switch in the kernel); it may change a summation order, so the two `offset1` arrangements -- and no other form -- are
+    held to the fp64 rule instead of equality."""
 
-    def __init__(self, name, make, call, diff, ref, atomic=(), dirty=None, images=True, elementwise=None, half=(), vjp=None):
+    def __init__(self, name, make, call, diff, ref, atomic=(), dirty=None, images=True, elementwise=None, half=(), vjp=None,
+                 refuses=None, unaligned=None):
         self.name, self.make, self.call, self.diff, self.ref = name, make, call, tuple(diff), ref
         self.atomic, self.dirty, self.images = frozenset(atomic), dirty, images
         self.elementwise, self.half, self.vjp = elementwise, frozenset(half), vjp
+        self.refuses, self.unaligned = {k: frozenset(v) for k, v in (refuses or {}).items()}, unaligned
         self._ref = {}
 
     def __repr__(self):
@@ -216,7 +226,10 @@ class Report:
     pruned / full), with the configuration and the tensor it came from; printed in the project's record(...) style"""
 
     def __init__(self):
-        self.worst = {}
+        self.worst, self.notes = {}, []
+
+    def note(self, node, text):
+        self.notes.append((str(node), text))
 
     def add(self, node, config, name, r):
         key = (str(node), config.split()[0].rstrip(":"))
@@ -225,8 +238,9 @@ class Report:
 
     def lines(self, node=None):
         """the table, or the rows of one node"""
-        return [f"{n} [{c}]: worst error/bound {r:.4f} ({where})" for (n, c), (r, where) in self.worst.items()
-                if node is None or n == str(node)]
+        return ([f"{n} [{c}]: worst error/bound {r:.4f} ({where})" for (n, c), (r, where) in self.worst.items()
+                 if node is None or n == str(node)]
+                + [f"{n} [{text}]" for n, text in self.notes if node is None or n == str(node)])
 
 
 def check_fp64(node, grads, need, use, kind, report, config):
@@ -371,6 +385,191 @@ def check_pruned_then_full(node, device, report, first_use):
     complaints = node.dirty(outs) if node.dirty is not None else []
     assert not complaints, f"{node}: state left behind by the full pass after a pruned one: {complaints}"
     check_fp64(node, run(node, device), node.diff, None, "random", report, "full pass over a new graph after a pruned one")
+
+
+# ---- the memory forms of the inputs ---------------------------------------------------------------------------------------
+INPUT_FORMS = ("format", "transposed", "slice", "offset12", "offset1")
+NOT_DENSE = ("format", "transposed", "slice")   # the forms that `is_contiguous()` can tell from a fresh tensor
+
+
+def _filler(t):
+    """what surrounds the values in a larger buffer: NaN, or the largest value of a format that has none"""
+    return float("nan") if t.is_floating_point() else (True if t.dtype == torch.bool else torch.iinfo(t.dtype).max)
+
+
+def input_form(values, form, device):
+    """the same values, in the same logical shape, in one of the five memory forms; None where the form does not apply
+    to the rank.  `values` is what Node.make returned for the input: contiguous or, for a 4-D image, channels_last."""
+    v = values.to(device)
+    if v.dim() == 0:
+        return None
+    if form == "format":
+        if v.dim() == 4:  # the OTHER format: channels_last for an NCHW-contiguous image, NCHW for a channels_last one
+            t = v.contiguous(memory_format=torch.channels_last) if v.is_contiguous() else v.contiguous()
+            return t.clone(memory_format=torch.preserve_format)
+        if v.dim() == 5:  # (as cot_form: the memory of a contiguous [B,C,D,H,W] viewed back)
+            return v.permute(0, 4, 1, 2, 3).contiguous().permute(0, 2, 3, 4, 1)
+        return None
+    if form == "transposed":
+        return v.transpose(-1, -2).contiguous().transpose(-1, -2) if v.dim() >= 2 else None
+    if form == "slice":
+        if v.dim() == 1:  # every other element of a buffer twice as long
+            buf = torch.full((2 * v.numel() + 1,), _filler(v), dtype=v.dtype, device=device)
+            t = buf[1::2]
+        else:
+            pad = [0] * v.dim()
+            pad[1] += 2
+            pad[-1] += 3
+            buf = torch.full([n + p for n, p in zip(v.shape, pad)], _filler(v), dtype=v.dtype, device=device)
+            idx = [slice(None)] * v.dim()
+            idx[1], idx[-1] = slice(1, 1 + v.shape[1]), slice(2, 2 + v.shape[-1])   # (a matrix: one dimension is both)
+            t = buf[tuple(idx)]
+        t.copy_(v)
+        assert t.shape == v.shape and (not t.is_contiguous() or v.numel() <= 1)
+        return t
+    if form in ("offset12", "offset1"):  # one element: 4 bytes past 16-byte alignment for fp32, 2 for fp16, 1 for bytes
+        off, n = int(form[6:]), v.numel()
+        dense = 1 + sum((sz - 1) * st for sz, st in zip(v.shape, v.stride())) == n or n == 0
+        assert dense, "Node.make returns dense tensors"
+        buf = torch.full((n + 2 * off + 12,), _filler(v), dtype=v.dtype, device=device)
+        t = buf[off:off + n].as_strided(v.shape, v.stride())  # (the strides of the fresh input: its own layout, moved)
+        t.copy_(v)
+        assert t.storage_offset() == off and t.is_contiguous() == v.is_contiguous()
+        return t
+    raise ValueError(form)
+
+
+def run_inputs(node, device, forms):
+    """(outputs, gradients) with the inputs named in `forms` {name: form} in that memory form and every other one fresh;
+    every differentiable input requires a gradient, the cotangents are fresh.  None where no named form applies."""
+    inp = node.make(device)
+    hit = False
+    for k, form in forms.items():
+        if not isinstance(inp.get(k), torch.Tensor):
+            continue
+        t = input_form(inp[k], form, device)
+        if t is not None:
+            inp[k], hit = t, True
+    if forms and not hit:
+        return None
+    for k in node.diff:
+        inp[k] = (inp[k] if k in forms else inp[k].clone(memory_format=torch.preserve_format)).requires_grad_()
+        assert inp[k].is_leaf
+    outs = _tuple(node.call(inp))
+    idx = [k for k in range(len(outs)) if outs[k].requires_grad]
+    if not node.diff:   # (a plain function, no autograd node: outputs only)
+        return tuple(outs), {}
+    cots = [cot_form(cot_values(outs[k].shape, k), "fresh", device, "random") for k in idx]
+    gs = torch.autograd.grad([outs[k] for k in idx], [inp[k] for k in node.diff], cots, allow_unused=True)
+    for k, g in zip(node.diff, gs):
+        assert g is None or g.shape == inp[k].shape, f"{node}: gradient of {k} has shape {tuple(g.shape)}, its input {tuple(inp[k].shape)}"
+    return tuple(outs), dict(zip(node.diff, gs))   # (the outputs still attached: Node.dirty walks their graph)
+
+
+def out_reference(node):
+    """the outputs of the reference on the CPU in fp64 and fp32 (for the `unaligned` routes, whose outputs may differ)"""
+    if "outs" not in node._ref:
+        res = []
+        for dt in (torch.float64, torch.float32):
+            with torch.no_grad():
+                inp = {k: (v.to(dt) if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in node.make("cpu").items()}
+                res.append([o.double() for o in _tuple(node.ref(inp))])
+        node._ref["outs"] = tuple(res)
+    return node._ref["outs"]
+
+
+def _tensor_inputs(node, device):
+    return [k for k, v in node.make(device).items() if isinstance(v, torch.Tensor)]
+
+
+def _refused(node, forms, device):
+    """the inputs of this arrangement that the node declares it refuses -- where the form applies to the input's rank and
+    its strides differ from the fresh input's (channels_last of one channel is the fresh tensor: nothing to refuse)"""
+    probe, out = node.make(device), []
+    for k, form in forms.items():
+        if form in node.refuses.get(k, node.refuses.get("*", ())) and isinstance(probe.get(k), torch.Tensor):
+            t = input_form(probe[k], form, device)
+            if t is not None and (t.stride() != probe[k].stride() or t.storage_offset() != probe[k].storage_offset()):
+                out.append(k)
+    return out
+
+
+def _device_fault(e):
+    """a HIP error surfaces as a RuntimeError too"""
+    return any(w in str(e) for w in ("HIP error", "hipError", "illegal memory access"))
+
+
+def check_input_forms(node, device, report):
+    """each input alone in each memory form that applies to its rank, all inputs in `format`, all inputs in `offset1`,
+    against the run on fresh inputs: every output and every gradient has the fresh one's logical shape (a gradient its
+    input's) and, read logically, the fresh one's values -- torch.equal, except the float-atomic gradients (fp64 rule or
+    element-wise model, as everywhere) and, for a node with a documented `unaligned` route, the two `offset1` arrangements
+    (fp64 rule, outputs included).  A form that the node declares in `refuses` must raise RuntimeError; any other
+    exception, and any undeclared one, fails.
+
+    Measured on an MI355X (tests/test_gpu_autograd_contract.py and tests/test_gpu_torch_ops.py print the table): every output
+    and every non-atomic gradient of every node equal in every accepted arrangement; no node needed `unaligned`.  Worst
+    error / bound of the atomic gradients over all arrangements: 3-D weight gradients (conv_bn, azhip.conv3d, fork net,
+    costvol_conv, conv_logits) 0.0004 .. 0.0021; 2-D weight gradients (convbn_unit, BasicBlock) 0.0006 .. 0.0015; softargmin
+    and azhip.softargmin d/dlogits 0.0096 and warp_gather / azhip.warp_gather d/dimg 0.539 of their element-wise bounds;
+    ConvGRU d/dwr 0.170 (f16x1) and 0.926 (bf16, bf16_ops), gru._Conv3x3Bf16 d/dw 0.196 -- the figures of the fresh run, the
+    operand rounding dominates; CorrBlock1D d/df1 0.0068.  Refused, per node: Node.refuses in the two test files."""
+    fresh = run_inputs(node, device, {})
+    assert fresh is not None
+    f_outs, f_grads = tuple(o.detach() for o in fresh[0]), fresh[1]
+    names = _tensor_inputs(node, device)
+    plans = [({k: form}, f"input {k}/{form}") for k in names for form in INPUT_FORMS]
+    plans += [({k: "format" for k in names}, "input all/format"), ({k: "offset1" for k in names}, "input all/offset1")]
+    atomic = tuple(k for k in node.diff if k in node.atomic)
+    for forms, config in plans:
+        refused = _refused(node, forms, device)
+        if refused:
+            try:
+                run_inputs(node, device, forms)
+            except RuntimeError as e:   # the wrapper's or the library's refusal -- a device fault is none
+                assert not _device_fault(e), f"{node} [{config}]: a device fault where a refusal is declared: {e}"
+            else:
+                raise AssertionError(f"{node} [{config}]: DID NOT RAISE the RuntimeError it declares for {','.join(refused)}")
+            report.note(node, f"{config}: refused ({','.join(refused)})")
+            continue
+        try:
+            got = run_inputs(node, device, forms)
+        except (RuntimeError, TypeError, ValueError) as e:
+            if _device_fault(e):
+                raise
+            raise AssertionError(f"{node} [{config}]: raised {type(e).__name__} for a form it does not declare as refused: {e}") from e
+        if got is None:
+            continue
+        outs, grads = got
+        complaints = node.dirty(outs) if node.dirty is not None else []
+        assert not complaints, f"{node} [{config}]: state left behind by backward: {complaints}"
+        outs = tuple(o.detach() for o in outs)
+        loose = node.unaligned is not None and config.endswith("/offset1")
+        assert len(outs) == len(f_outs)
+        for j, (o, f) in enumerate(zip(outs, f_outs)):
+            assert o.shape == f.shape, f"{node} [{config}]: output {j} has shape {tuple(o.shape)}, fresh {tuple(f.shape)}"
+            if loose:
+                o64, o32 = out_reference(node)
+                r = ratio(o, o64[j], o32[j])
+                report.add(node, config, f"output {j}", r)
+                assert r <= 1.0, f"{node} [{config}]: output {j} misses the fp64 rule, error/bound {r:.3f}"
+            else:
+                assert torch.equal(o.contiguous(), f.contiguous()), (
+                    f"{node} [{config}]: output {j} differs from the fresh run, max {float((o - f).abs().max()):.3e}")
+        for k in node.diff:
+            g, f = grads[k], f_grads[k]
+            assert (g is None) == (f is None), f"{node} [{config}]: gradient of {k} is {'None' if g is None else 'a tensor'}"
+            if g is None:
+                continue
+            assert g.shape == f.shape, f"{node} [{config}]: gradient of {k} has shape {tuple(g.shape)}, fresh {tuple(f.shape)}"
+            if k not in node.atomic and not loose:
+                assert torch.equal(g.contiguous(), f.contiguous()), (
+                    f"{node} [{config}]: d/d{k} differs from the fresh run, max {float((g - f).abs().max()):.3e}")
+        held = node.diff if loose else atomic
+        if held:
+            check_fp64(node, grads, held, None, "random", report, config)
+        else:
+            report.add(node, config, "all (equal)", 0.0)
 
 
 # ---- module-level state ---------------------------------------------------------------------------------------------------

@@ -39,6 +39,17 @@ from tests.test_gpu_raft_corr import _torch_reference as _corr_reference  # noqa
 DEV = "cuda:0"
 EPS = 1e-5
 RELU_MARGIN = 1e-5
+# what the wrappers REFUSE (H.Node.refuses), as measured by H.check_input_forms: a `_chk` without `.contiguous()` refuses the
+# forms that are not dense-contiguous; the library refuses (AZ_EINVAL) a pointer that is not 16-byte aligned where a kernel
+# loads float4 unconditionally -- az_absmax on the operands of the f16x3 / one-part convolutions, az_cost_volume_fwd_ndhwc,
+# az_spp_upsample_fwd, az_costconv_assemble_fwd; BatchNorm's gamma and beta are read through their pointers.
+STRIDED, UNALIGNED, PARAM = H.NOT_DENSE, ("offset1",), ("slice",)
+
+
+def _bn_refusals(weights=("weight",), affine=("gamma", "beta"), x=STRIDED + UNALIGNED, extra=None):
+    r = {"x": x, **{k: UNALIGNED for k in weights}, **{k: PARAM for k in affine}}
+    r.update(extra or {})
+    return {k: v for k, v in r.items() if v}
 
 
 def _plant(unit, weight, gamma, beta, rm=None, rv=None):
@@ -117,7 +128,8 @@ def _convbn_node(mode, cin, cout, xshape, relu, res, train, arith):
         return fn(i["x"], unit, relu=relu, add=i.get("residual"), arith=conv3d.Arith.of(arith))
 
     diff = ("x", "weight", "gamma", "beta") + (("residual",) if res else ())
-    return H.Node(name, make, call, diff, lambda i: F.relu(pre(i)) if relu else pre(i), atomic=("weight",))
+    return H.Node(name, make, call, diff, lambda i: F.relu(pre(i)) if relu else pre(i), atomic=("weight",),
+                  refuses=_bn_refusals(extra={"residual": STRIDED}))
 
 
 S1, S2, T2 = conv3d.CONV_S1, conv3d.CONV_S2, conv3d.DECONV_S2
@@ -179,7 +191,10 @@ def _unit2d_node(cin, cout, stride, relu, res, train, groups, skip=False):
         return (y, i["x"] * 1.0) if skip else y
 
     diff = ("x", "weight", "gamma", "beta") + (("residual",) if res else ())
-    return H.Node(name, make, call, diff, ref, atomic=("weight",))
+    # stride 1: az_absmax of x and of the weight; the stride-2 volume route packs its weight first; the 3-channel patches
+    # route reads neither through a float4
+    refuses = _bn_refusals(x=UNALIGNED) if stride == 1 else _bn_refusals((), x=UNALIGNED if cin == 32 else ())
+    return H.Node(name, make, call, diff, ref, atomic=("weight",), refuses=refuses)
 
 
 UNIT2D = [
@@ -215,7 +230,7 @@ def _logits_node(addend):
         return y + i["addend"] if addend else y
 
     return H.Node(f"conv_logits{' +addend' if addend else ''}", make, call, ("x", "weight") + (("addend",) if addend else ()),
-                  ref, atomic=("weight",))
+                  ref, atomic=("weight",), refuses={"x": STRIDED})
 
 
 def _deferred_node():
@@ -250,11 +265,12 @@ def _deferred_node():
         return agg3d.conv_logits(t, conv, add=i["addend"], affine=defer)
 
     return H.Node(name, make, call, ("x", "weight", "gamma", "beta", "w1", "addend"),
-                  lambda i: F.conv3d(F.relu(pre(i)), i["w1"], padding=1)[:, 0] + i["addend"], atomic=("weight", "w1"))
+                  lambda i: F.conv3d(F.relu(pre(i)), i["w1"], padding=1)[:, 0] + i["addend"], atomic=("weight", "w1"),
+                  refuses=_bn_refusals())
 
 
 ADD = H.Node("add", lambda dev: {"a": seeded(V32, 4401).to(dev), "b": seeded(V32, 4402).to(dev)},
-             lambda i: agg3d.add(i["a"], i["b"]), ("a", "b"), lambda i: i["a"] + i["b"])
+             lambda i: agg3d.add(i["a"], i["b"]), ("a", "b"), lambda i: i["a"] + i["b"], refuses={"a": STRIDED, "b": STRIDED})
 
 
 def _fanout_node(n):
@@ -358,7 +374,7 @@ def _ops_nodes():
     yield H.Node("cost_volume_ndhwc", lambda dev: {k: nhwc(v) for k, v in feats(dev).items()},
                  lambda i: ops.cost_volume_ndhwc(i["fl"], i["fr"], 4), ("fl", "fr"),
                  lambda i: po.build_cost_volume(i["fl"].permute(0, 3, 1, 2), i["fr"].permute(0, 3, 1, 2), 4).permute(0, 2, 3, 4, 1),
-                 elementwise=_cv_elementwise("ndhwc"))
+                 elementwise=_cv_elementwise("ndhwc"), refuses={"fl": UNALIGNED, "fr": UNALIGNED})
     yield H.Node("softargmin", lambda dev: {"logits": seeded((1, 6, 3, 5), 4610, -3.0, 3.0).to(dev)},
                  lambda i: ops.softargmin(i["logits"]), ("logits",),
                  lambda i: po.soft_argmin_head(i["logits"][:, None], 24, 12, 20), atomic=("logits",),
@@ -413,6 +429,30 @@ def _ops_nodes():
                  ("q0", "q1", "q2"), lambda i: rh.sequence_loss([i["q0"], i["q1"], i["q2"]], i["gt"], i["valid"]),
                  images=False, elementwise=_seq_loss_elementwise)
 
+    # K29: three scales of one ground truth (ops.multiscale_disp_loss); the reference is utils/disp_losses.py's formula
+    MS_SHIFTS, MS_WEIGHTS = (0, 1, 2), (1.0, 0.7, 0.5)
+
+    def ms_inputs(dev):
+        gt = seeded((2, 1, 9, 13), 4636, 0.0, 40.0)
+        i = {"gt": gt, "mask": seeded((2, 1, 9, 13), 4637) > -0.6}
+        for k, s in enumerate(MS_SHIFTS):
+            at = gt[:, :, ::1 << s, ::1 << s][:, :, :9 >> s, :13 >> s]
+            i[f"p{k}"] = at + seeded(tuple(at.shape), 4638 + k, -2.5, 2.5)
+        return {k: v.to(dev) for k, v in i.items()}
+
+    def ms_ref(i):
+        total = 0.0
+        for k, (s, wt) in enumerate(zip(MS_SHIFTS, MS_WEIGHTS)):
+            p = i[f"p{k}"]
+            pick = lambda t: t[:, :, ::1 << s, ::1 << s][:, :, :p.shape[2], :p.shape[3]]
+            m = pick(i["mask"])
+            total = total + wt * F.smooth_l1_loss(p[m], pick(i["gt"])[m], reduction="mean")
+        return total
+
+    yield H.Node("multiscale_disp_loss", ms_inputs,
+                 lambda i: ops.multiscale_disp_loss([i["p0"], i["p1"], i["p2"]], i["gt"], i["mask"], MS_SHIFTS, MS_WEIGHTS),
+                 ("p0", "p1", "p2"), ms_ref, images=False)
+
     def spp_inputs(dev):
         i = {"raw": seeded((1, 64, 8, 12), 4670), "skip": seeded((1, 128, 8, 12), 4671)}
         for k, hw in enumerate(((1, 1), (2, 3), (3, 5), (4, 6))):
@@ -423,7 +463,8 @@ def _ops_nodes():
     yield H.Node("spp_concat", spp_inputs, lambda i: sub3.spp_concat(i["raw"], i["skip"], branches(i)),
                  ("raw", "skip", "b0", "b1", "b2", "b3"),
                  lambda i: torch.cat([i["raw"], i["skip"]] + [F.interpolate(t, size=(8, 12), mode="bilinear", align_corners=True)
-                                                              for t in branches(i)], 1), elementwise=_spp_elementwise)
+                                                              for t in branches(i)], 1), elementwise=_spp_elementwise,
+                 refuses={f"b{k}": UNALIGNED for k in range(4)})
 
     # costconv._Merge and _Assemble, through the fused cost-volume convolution that owns them
     yield H.Node("costvol_conv", lambda dev: {"fl": seeded((2, 32, 6, 12), 4690).to(dev), "fr": seeded((2, 32, 6, 12), 4691).to(dev),
@@ -440,7 +481,7 @@ def _ops_nodes():
                                                         "weight": procedural_tensor("contract.op.w", (32, 32, 3, 3, 3)).to(dev)},
                  lambda i: torch.ops.azhip.conv3d(i["x"], i["weight"], S1), ("x", "weight"),
                  lambda i: F.conv3d(i["x"].permute(0, 4, 1, 2, 3), i["weight"], padding=1).permute(0, 2, 3, 4, 1),
-                 atomic=("weight",))
+                 atomic=("weight",), refuses={"x": UNALIGNED, "weight": UNALIGNED})
 
 
 # ---- costconv._Assemble and _Merge, called directly: each backward is one launch with an element-wise model ------------------
@@ -475,7 +516,7 @@ def _assemble_elementwise(i, cots, got, memo):
 ASSEMBLE = H.Node("costconv._Assemble", lambda dev: {k: seeded(sh, 4900 + j).to(dev)
                                                      for j, (k, sh) in enumerate(zip(("fb", "fe", "g"), V.asm_shapes(ASM)))},
                   lambda i: costconv._Assemble.apply(i["fb"], i["fe"], i["g"], ASM[3]), ("fb", "fe", "g"), _assemble_ref,
-                  elementwise=_assemble_elementwise)
+                  elementwise=_assemble_elementwise, refuses={k: STRIDED + UNALIGNED for k in ("fb", "fe", "g")})
 
 
 def _merge_masks(dev):
@@ -550,7 +591,8 @@ def _block_node(down):
         return blk(i["x"], groups=2, arith=conv3d.Arith.of("f16x3"))
 
     diff = ["x"] + [p + u for u in units for p in ("w", "g", "b")]
-    return H.Node(name, make, call, diff, ref, atomic=["w" + u for u in units])
+    return H.Node(name, make, call, diff, ref, atomic=["w" + u for u in units],
+                  refuses=_bn_refusals(("w2", "wd") if down else ("w1", "w2"), [p + u for u in units for p in ("g", "b")], UNALIGNED))
 
 
 BLOCKS = [_block_node(False), _block_node(True)]
@@ -791,6 +833,32 @@ def test_first_layer_token_and_the_sink_is_closed(need_x, capsys):
     H.same(FIRST, grads, H.run(FIRST, DEV, need), need, "armed sink vs no sink")
 
 
+LAST_SINK = []
+
+
+def _first_sink_node():
+    """the first layer as the models run it: an armed overlap.Sink whose token is the fourth input of conv2d._ConvS2Patches and
+    whose _Gate aliases stand for the weight; `dirty` asks that the pass's sink is joined and empty after every backward"""
+    def call(i):
+        unit = _plant(sub3.convbn(3, 32, 3, 2, 1, 1).to(DEV).train(), i["weight"], i["gamma"], i["beta"], i["rm"], i["rv"])
+        sink = overlap.begin(unit, i["x"])
+        assert sink is not None and sink.token.requires_grad
+        LAST_SINK[:] = [sink]
+        y = sub3._convbn_unit(i["x"], unit, relu=True, groups=2, arith=conv3d.Arith.of("f16x3")._replace(sink=sink))
+        assert sink.armed and sink.live
+        return y
+
+    def dirty(outs):
+        k = LAST_SINK[0]
+        return [] if (k.joined and not k.live and not k.pending and not k.keep and k.arena is None) else ["the sink is still open"]
+
+    return H.Node("convbn_unit 3->32 s2 train g2 relu, armed sink", FIRST.make, call, FIRST.diff, FIRST.ref, atomic=("weight",),
+                  dirty=dirty, refuses=FIRST.refuses)
+
+
+FIRST_SINK = _first_sink_node()
+
+
 # ---- several consumers of one tensor: handover.GradSlot --------------------------------------------------------------------------
 def _fork_node():
     names = [f"{p}{k}" for k in range(4) for p in ("w", "g", "b")]
@@ -832,7 +900,8 @@ def _fork_node():
                  for k in range(4)]
         return _fork_net(i["x"], units, conv3d.Arith.of("f16x3"))
 
-    return H.Node("fork net", make, call, ["x"] + names, ref, atomic=[f"w{k}" for k in range(4)], dirty=H.slot_complaints)
+    return H.Node("fork net", make, call, ["x"] + names, ref, atomic=[f"w{k}" for k in range(4)], dirty=H.slot_complaints,
+                  refuses=_bn_refusals([f"w{k}" for k in range(4)], [f"{p}{k}" for k in range(4) for p in ("g", "b")]))
 
 
 FORK = _fork_node()
@@ -872,3 +941,36 @@ def test_the_slots_are_there_to_be_checked(monkeypatch):
     assert slot is not None and slot.expect == 3 and not H.slot_complaints(outs)
     slot.left -= 1
     assert H.slot_complaints(outs)
+
+
+# ---- the memory form of the INPUTS: strides, storage offsets, alignment (H.check_input_forms) ---------------------------------
+def _sum_parts_node(n):
+    """handover.sum_parts is no autograd node: a plain sum of n gradients of one tensor, whose first part arrives in the other
+    memory format (a plain torch consumer may hand back such a gradient)"""
+    def make(dev):
+        i = {f"p{k}": seeded(V32, 4960 + k).to(dev) for k in range(n)}
+        i["p0"] = H.input_form(i["p0"], "format", dev)
+        return i
+
+    return H.Node(f"sum_parts n={n}", make, lambda i: handover_mod.sum_parts([i[f"p{k}"] for k in range(n)]), (),
+                  lambda i: sum(i[f"p{k}"] for k in range(n)))
+
+
+SUM_PARTS = [_sum_parts_node(n) for n in (2, 4, 5)]
+INPUT_NODES = ALL + [CORR, FORK, FIRST_SINK] + SUM_PARTS
+
+
+@pytest.mark.parametrize("node", INPUT_NODES, ids=ids(INPUT_NODES))
+def test_input_forms(node, capsys):
+    record(capsys, node, H.check_input_forms)
+
+
+@pytest.mark.parametrize("node", SUM_PARTS, ids=ids(SUM_PARTS))
+def test_sum_parts_with_the_first_part_in_the_other_format(node):
+    """the sum has the parts' logical shape and, read logically, their sum's values (fp64 rule): before its fix sum_parts
+    allocated the result *_like the first part and az_sum4 wrote it linearly, a permuted sum"""
+    i = node.make(DEV)
+    assert not i["p0"].is_contiguous()
+    out = node.call(i)
+    o64, o32 = H.out_reference(node)
+    assert out.shape == o64[0].shape and H.ratio(out, o64[0], o32[0]) <= 1.0
