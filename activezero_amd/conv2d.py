@@ -17,6 +17,7 @@ triplet image made per call (memoised between no_grad forwards).
        (firstconv.0)
     1x1 stride 2 (layer2.0.downsample)     subsample + 1x1             (autograd of the slice)   1x1 wgrad
 """
+import collections
 import os
 
 import torch
@@ -40,23 +41,180 @@ def image(r):
     return r.permute(0, 3, 1, 2)
 
 
-def _pack(weight, cin, cout, ci_real, co_real, s_out, s_in, kh, kw, flip, cache=False):
+PEAK_F16 = conv3d._PEAK_F16
+PEAK_BF16 = (2500.0, "dense bf16 MFMA peak")
+
+
+# ---- the forward kernels (include/azhip.h K13 / K13r), one row each: what differs between them ------------------------------
+def _x6_floats(cin, cout, kh, kw):
+    n = _lib.lib().az_conv2d_packed_floats(cin, cout, kh, kw)
+    if n < 0:
+        raise RuntimeError(f"conv2d: unsupported channel counts cin={cin} cout={cout}")
+    return n
+
+
+def _roll_floats(cin, cout, kh, kw):
+    return int(_lib.lib().az_conv2d_roll_packed_floats(cin, cout))
+
+
+def _parts(n):
+    """floats of an image of n 16-bit parts per weight"""
+    return lambda cin, cout, kh, kw: kh * kw * cin * cout * n // 2
+
+
+def _stats_tiles(groups, b, h, w, cin, cout):
+    return int(_lib.lib().az_conv2d_stats_tiles(b, h, w, groups))
+
+
+def _stats_rows(groups, b, h, w, cin, cout):
+    nrows = int(_lib.lib().az_conv2d_roll_stats_rows(groups, b, h, w, cin, cout))
+    if nrows <= 0:
+        raise RuntimeError(f"az_conv2d_roll_stats_rows: {nrows}")
+    return nrows
+
+
+# amax operands of an entry: none; slots handed on as the caller gives them (None: that operand unscaled); or every
+# operand scaled (f16x3), a missing one taken here
+NO_AMAX, AMAX_GIVEN, AMAX_TAKEN = range(3)
+# what follows `cin, cout` in a launch: in / out / residual pixel strides + kh, kw, dilation; nothing (dense 3x3 d1); the
+# one-part kernels' pixel strides (input, output, residual, the two gates; 3x3 d1)
+GENERIC, ROLL, ONE_PART = range(3)
+# pack:  the pack entry; a pair (forward, flipped) where the ABI has two entries instead of a `flip` argument
+# stats: (the entry that also writes BatchNorm partials, rows per statistic group of them) or None
+# affine: the wrapper launches it with scale / shift / ReLU; False: the residual only (one-part: bias / act / gates instead)
+# plan:  the packing.PACK_2D_* kind of its images in the pack plan, None: the plan holds none
+Kernel = collections.namedtuple("Kernel", "pack floats fwd stats amax tail affine plan peak")
+KERNELS = {
+    "gather bf16x6": Kernel("az_conv2d_pack_weights", _x6_floats, "az_conv2d_fwd", ("az_conv2d_fwd_stats", _stats_tiles),
+                            NO_AMAX, GENERIC, True, None, PEAK_X6),
+    "gather f16x3": Kernel("az_conv2d_pack_weights_f16", _parts(2), "az_conv2d_fwd_f16", ("az_conv2d_fwd_stats_f16", _stats_tiles),
+                           AMAX_TAKEN, GENERIC, True, packing.PACK_2D_SAME, PEAK_F16),
+    "roll bf16x6": Kernel("az_conv2d_roll_pack", _roll_floats, "az_conv2d_roll_fwd", ("az_conv2d_roll_fwd_stats", _stats_rows),
+                          NO_AMAX, ROLL, True, None, PEAK_X6),
+    "roll f16x3": Kernel("az_conv2d_roll_pack_f16", _parts(2), "az_conv2d_roll_fwd_f16", ("az_conv2d_roll_fwd_stats_f16", _stats_rows),
+                         AMAX_TAKEN, ROLL, False, packing.PACK_2D_ROLL, PEAK_F16),
+    # the ConvGRU's (nets/raft/gru.py): one 16-bit part per operand, the weight image unscaled
+    "one-part bf16": Kernel(("az_conv2d_pack_weights_bf16", "az_conv2d_pack_weights_bf16_flipped"), _parts(1), "az_conv2d_bf16_fwd",
+                            None, NO_AMAX, ONE_PART, True, None, PEAK_BF16),
+    "one-part h1": Kernel("az_conv2d_pack_weights_h1", _parts(1), "az_conv2d_h1_fwd", None, AMAX_GIVEN, ONE_PART, True, None,
+                          PEAK_BF16),
+}
+GATHER_X6, GATHER_F16, ROLL_X6, ROLL_F16, ONE_BF16, ONE_H1 = KERNELS.values()
+
+
+def _pack_image(k, weight, cin, cout, s_out, s_in, kh=3, kw=3, flip=False, ci_real=None, co_real=None, cache=False):
+    """(image of `weight` for kernel k, device scalar max |w| where the image is scaled by it, else None).  s_out / s_in:
+    strides of the cout / cin index in the stored weight; ci_real / co_real (GENERIC): the channels that exist, the rest
+    of cin / cout is zero padding.  cache: memoised between no_grad forwards (packing.memo)."""
+    ci_real, co_real = cin if ci_real is None else ci_real, cout if co_real is None else co_real
     w = _chk(weight.detach().contiguous(), "weight")
+    pair = isinstance(k.pack, tuple)
+
+    def pack_now(packed, w_amax):
+        args = [_p(packed), _p(w), _p(w_amax)] if k.amax else [_p(packed), _p(w)]
+        args += (cin, cout, ci_real, co_real, s_out, s_in) if k.tail == GENERIC else (cin, cout, s_out, s_in)
+        if pair or k.tail == GENERIC:
+            args += (kh, kw)
+        if not pair:
+            args.append(int(flip))
+        _call(k.pack[bool(flip)] if pair else k.pack, *args, _stream())
 
     def make():
-        n = _lib.lib().az_conv2d_packed_floats(cin, cout, kh, kw)
-        if n < 0:
-            raise RuntimeError(f"conv2d: unsupported channel counts cin={cin} cout={cout}")
-        packed = torch.empty(n, dtype=torch.float32, device=w.device)
-        _call("az_conv2d_pack_weights", _p(packed), _p(w), cin, cout, ci_real, co_real, s_out, s_in, kh, kw,
-              int(flip), _stream())
-        return packed
+        w_amax = weight_amax(weight, w) if k.amax == AMAX_TAKEN else None
+        packed = torch.empty(k.floats(cin, cout, kh, kw), dtype=torch.float32, device=w.device)
+        pack_now(packed, w_amax)
+        return packed, w_amax
 
-    key = (packing.cache_key(weight), cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip)) if cache else None
-    return packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
+    if cache:
+        key = (k.fwd, packing.cache_key(weight), cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip))
+        hit = packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
+        if hit[1] is not None:
+            debug_check(w, hit[1])
+        return hit
+    hit = None
+    if k.plan is not None:
+        hit = packing.planned_pack(weight, w, k.plan, cin, cout, ci_real, co_real, s_out, s_in, kh * kw, flip, pack_now)
+    return hit if hit is not None else make()
 
 
-PEAK_F16 = conv3d._PEAK_F16
+def _launch(k, xr, packed, cin, cout, kh=3, kw=3, dil=1, amax=None, scale=None, shift=None, res=None, relu=False,
+            tag="conv2d", stats=None, bias=None, act=0, gates=(None, None)):
+    """Kernel k on xr: [B,H,W,Cx] rows with Cx >= cin; returns relu?(conv(xr) * scale + shift + res) as [B,H,W,cout] rows.
+    amax: (amax array of xr, of the weight) for the rows that take them.  `stats` (a bn2d.Partials): the launch without
+    epilogue operands that also fills it with the output's BatchNorm partials.  ONE_PART rows (nets/raft/gru.py) return
+    act(conv(xr) + bias + res) -- act an ACT_* code, gates = (gate_z, gate_h) rows for ACT_GRU -- and take no scale / shift /
+    relu; the other rows take no bias / act / gates.  An operand the row's launch does not take: TypeError."""
+    b, h, w, cx = xr.shape
+    one = k.tail == ONE_PART
+    if (amax is None) == bool(k.amax):
+        raise TypeError(f"{k.fwd} takes {'an' if k.amax else 'no'} amax pair")
+    affine = scale is not None or shift is not None or relu
+    if (affine and (one or not k.affine)) or (not one and (bias is not None or act or gates[0] is not None or gates[1] is not None)):
+        raise TypeError(f"{k.fwd} is not launched with these epilogue operands")
+    if k.tail == ROLL and not (kh == 3 and kw == 3 and dil == 1):
+        raise RuntimeError(f"{k.fwd}: 3x3, dilation 1 only")
+    out = xr.new_empty(b, h, w, cout)
+    am = (_p(amax[0]), _p(amax[1])) if k.amax else ()
+    io = () if k.tail == ROLL else (cx, cout)
+    geo = (kh, kw, dil) if k.tail == GENERIC else ()
+    name = f"{tag}_{cin}_{cout}" if one else f"{tag}_{kh}x{kw}d{dil}_{cin}_{cout}"
+    flops = 2.0 * kh * kw * cin * cout * b * h * w
+    if stats is not None:
+        if k.stats is None or affine or res is not None:
+            raise TypeError(f"{k.fwd}: the launch with BatchNorm partials takes no epilogue operands")
+        entry, rows_of = k.stats
+        n = rows_of(stats.groups, b, h, w, cin, cout)
+        part, cnt = xr.new_empty(stats.groups, cout, n, 2), xr.new_empty(stats.groups, n)
+        stats.part, stats.cnt, stats.tiles = part, cnt, n
+        with profiler.scope(name, flops=flops, peak=k.peak):
+            _call(entry, _p(out), _p(part), _p(cnt), _p(xr), _p(packed), *am, stats.groups, b, h, w, cin, cout, *io, *geo,
+                  _stream())
+        return out
+    strides = (res.shape[-1] if res is not None else 0,) if k.tail != ROLL else ()
+    if one:
+        gz, gh = gates
+        ep = (_p(bias), _p(res), _p(gz), _p(gh), act)
+        strides += (gz.shape[-1] if gz is not None else 0, gh.shape[-1] if gh is not None else 0)
+    else:
+        ep = (_p(scale), _p(shift), _p(res), int(relu))
+    with profiler.scope(name, flops=flops, peak=k.peak):
+        _call(k.fwd, _p(out), _p(xr), _p(packed), *am, *ep, b, h, w, cin, cout, *io, *strides, *geo, _stream())
+    return out
+
+
+# ---- the per-kernel helpers the table replaced, with their signatures, as one row each: the suite's tests of before the table
+# (and tests/test_conv2d_call_trace_cpu.py, against calls recorded through the originals) reach the kernels by these names
+def _pack(weight, cin, cout, ci_real, co_real, s_out, s_in, kh, kw, flip, cache=False):
+    return _pack_image(GATHER_X6, weight, cin, cout, s_out, s_in, kh, kw, flip, ci_real, co_real, cache)[0]
+
+
+def _pack_f16(weight, cin, cout, ci_real, co_real, s_out, s_in, kh, kw, flip, cache=False):
+    return _pack_image(GATHER_F16, weight, cin, cout, s_out, s_in, kh, kw, flip, ci_real, co_real, cache)
+
+
+def _pack_roll(weight, cin, cout, s_out, s_in, flip, cache=False):
+    return _pack_image(ROLL_X6, weight, cin, cout, s_out, s_in, 3, 3, flip, cache=cache)[0]
+
+
+def _pack_roll_f16(weight, cin, cout, s_out, s_in, flip):
+    return _pack_image(ROLL_F16, weight, cin, cout, s_out, s_in, 3, 3, flip)
+
+
+def _run(xr, packed, cin, cout, kh, kw, dil, scale=None, shift=None, res=None, relu=False, tag="conv2d", stats=None):
+    return _launch(GATHER_X6, xr, packed, cin, cout, kh, kw, dil, None, scale, shift, res, relu, tag, stats)
+
+
+def _run_f16(xr, x_amax, packed, w_amax, cin, cout, kh, kw, dil, scale=None, shift=None, res=None, relu=False,
+             tag="conv2d", stats=None):
+    return _launch(GATHER_F16, xr, packed, cin, cout, kh, kw, dil, (x_amax, w_amax), scale, shift, res, relu, tag, stats)
+
+
+def _run_roll(xr, packed, cin, cout, scale=None, shift=None, res=None, relu=False, tag="conv2d", stats=None):
+    return _launch(ROLL_X6, xr, packed, cin, cout, 3, 3, 1, None, scale, shift, res, relu, tag, stats)
+
+
+def _run_roll_f16(xr, x_amax, packed, w_amax, cin, cout, res=None, tag="conv2d", stats=None):
+    return _launch(ROLL_F16, xr, packed, cin, cout, amax=(x_amax, w_amax), res=res, tag=tag, stats=stats)
 
 
 def _amax_of(t, r):
@@ -64,48 +222,6 @@ def _amax_of(t, r):
     over its rows r"""
     am = _get_amax(t)
     return am if am is not None else absmax(r)
-
-
-def _pack_f16(weight, cin, cout, ci_real, co_real, s_out, s_in, kh, kw, flip, cache=False):
-    """(packed f16x3 image, device scalar max |w|) -- az_conv2d_pack_weights_f16"""
-    w = _chk(weight.detach().contiguous(), "weight")
-
-    def pack_now(packed, w_amax):
-        _call("az_conv2d_pack_weights_f16", _p(packed), _p(w), _p(w_amax), cin, cout, ci_real, co_real, s_out, s_in, kh, kw,
-              int(flip), _stream())
-
-    def make():
-        w_amax = weight_amax(weight, w)
-        packed = torch.empty(kh * kw * cin * cout, dtype=torch.float32, device=w.device)
-        pack_now(packed, w_amax)
-        return packed, w_amax
-
-    if cache:
-        key = (packing.cache_key(weight), "f16", cin, cout, ci_real, co_real, s_out, s_in, kh, kw, bool(flip))
-        hit = packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
-        debug_check(w, hit[1])
-        return hit
-    hit = packing.planned_pack(weight, w, packing.PACK_2D_SAME, cin, cout, ci_real, co_real, s_out, s_in, kh * kw, flip, pack_now)
-    return hit if hit is not None else make()
-
-
-def _run_f16(xr, x_amax, packed, w_amax, cin, cout, kh, kw, dil, scale=None, shift=None, res=None, relu=False,
-             tag="conv2d", stats=None):
-    """_run on the f16x3 kernels"""
-    b, h, w, cx = xr.shape
-    out = xr.new_empty(b, h, w, cout)
-    with profiler.scope(f"{tag}_{kh}x{kw}d{dil}_{cin}_{cout}", flops=2.0 * kh * kw * cin * cout * b * h * w,
-                        peak=PEAK_F16):
-        if stats is not None:
-            tiles = int(_lib.lib().az_conv2d_stats_tiles(b, h, w, stats.groups))
-            part, cnt = xr.new_empty(stats.groups, cout, tiles, 2), xr.new_empty(stats.groups, tiles)
-            _call("az_conv2d_fwd_stats_f16", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), _p(x_amax), _p(w_amax),
-                  stats.groups, b, h, w, cin, cout, cx, cout, kh, kw, dil, _stream())
-            stats.part, stats.cnt, stats.tiles = part, cnt, tiles
-        else:
-            _call("az_conv2d_fwd_f16", _p(out), _p(xr), _p(packed), _p(x_amax), _p(w_amax), _p(scale), _p(shift), _p(res),
-                  int(relu), b, h, w, cin, cout, cx, cout, res.shape[-1] if res is not None else 0, kh, kw, dil, _stream())
-    return out
 
 
 def _up(n, m):
@@ -123,91 +239,6 @@ def _roll_ok(xr, cin, cout, kh, kw, dil, res=None):
             and xr.shape[0] * xr.shape[1] * xr.shape[2] * 256 < 0xffffff00)
 
 
-def _pack_roll(weight, cin, cout, s_out, s_in, flip, cache=False):
-    w = _chk(weight.detach().contiguous(), "weight")
-
-    def make():
-        packed = torch.empty(int(_lib.lib().az_conv2d_roll_packed_floats(cin, cout)), dtype=torch.float32, device=w.device)
-        _call("az_conv2d_roll_pack", _p(packed), _p(w), cin, cout, s_out, s_in, int(flip), _stream())
-        return packed
-
-    key = (packing.cache_key(weight), "roll", cin, cout, s_out, s_in, bool(flip)) if cache else None
-    return packing.memo(_PACK2D_CACHE, key, make, (weight,), 256)
-
-
-def _pack_roll_f16(weight, cin, cout, s_out, s_in, flip):
-    w = _chk(weight.detach().contiguous(), "weight")
-
-    def pack_now(packed, w_amax):
-        _call("az_conv2d_roll_pack_f16", _p(packed), _p(w), _p(w_amax), cin, cout, s_out, s_in, int(flip), _stream())
-
-    hit = packing.planned_pack(weight, w, packing.PACK_2D_ROLL, cin, cout, cin, cout, s_out, s_in, 9, flip, pack_now)
-    if hit is not None:
-        return hit
-    w_amax = weight_amax(weight, w)
-    packed = torch.empty(9 * cin * cout, dtype=torch.float32, device=w.device)
-    pack_now(packed, w_amax)
-    return packed, w_amax
-
-
-def _run_roll_f16(xr, x_amax, packed, w_amax, cin, cout, res=None, tag="conv2d", stats=None):
-    b, h, w, _ = xr.shape
-    out = xr.new_empty(b, h, w, cout)
-    with profiler.scope(f"{tag}_3x3d1_{cin}_{cout}", flops=2.0 * 9 * cin * cout * b * h * w, peak=PEAK_F16):
-        if stats is not None:
-            nrows = int(_lib.lib().az_conv2d_roll_stats_rows(stats.groups, b, h, w, cin, cout))
-            if nrows <= 0:
-                raise RuntimeError(f"az_conv2d_roll_stats_rows: {nrows}")
-            part, cnt = xr.new_empty(stats.groups, cout, nrows, 2), xr.new_empty(stats.groups, nrows)
-            _call("az_conv2d_roll_fwd_stats_f16", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), _p(x_amax), _p(w_amax),
-                  stats.groups, b, h, w, cin, cout, _stream())
-            stats.part, stats.cnt, stats.tiles = part, cnt, nrows
-        else:
-            _call("az_conv2d_roll_fwd_f16", _p(out), _p(xr), _p(packed), _p(x_amax), _p(w_amax), None, None, _p(res), 0,
-                  b, h, w, cin, cout, _stream())
-    return out
-
-
-def _run_roll(xr, packed, cin, cout, scale=None, shift=None, res=None, relu=False, tag="conv2d", stats=None):
-    """the batch-walking 3x3 kernel (az_conv2d_roll.hip); `stats`: as _run"""
-    b, h, w, _ = xr.shape
-    out = xr.new_empty(b, h, w, cout)
-    if stats is not None:
-        nrows = int(_lib.lib().az_conv2d_roll_stats_rows(stats.groups, b, h, w, cin, cout))
-        if nrows <= 0:
-            raise RuntimeError(f"az_conv2d_roll_stats_rows: {nrows}")
-        part, cnt = xr.new_empty(stats.groups, cout, nrows, 2), xr.new_empty(stats.groups, nrows)
-        stats.part, stats.cnt, stats.tiles = part, cnt, nrows
-    with profiler.scope(f"{tag}_3x3d1_{cin}_{cout}", flops=2.0 * 9 * cin * cout * b * h * w, peak=PEAK_X6):
-        if stats is not None:
-            _call("az_conv2d_roll_fwd_stats", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), stats.groups, b, h, w,
-                  cin, cout, _stream())
-        else:
-            _call("az_conv2d_roll_fwd", _p(out), _p(xr), _p(packed), _p(scale), _p(shift), _p(res), int(relu), b, h, w,
-                  cin, cout, _stream())
-    return out
-
-
-def _run(xr, packed, cin, cout, kh, kw, dil, scale=None, shift=None, res=None, relu=False, tag="conv2d", stats=None):
-    """xr: [B,H,W,Cx] rows with Cx >= cin; returns [B,H,W,cout] rows.  `stats` (a bn2d.Partials): the launch without
-    epilogue operands that also fills it with the output's BatchNorm partials."""
-    b, h, w, cx = xr.shape
-    out = xr.new_empty(b, h, w, cout)
-    if stats is not None:
-        tiles = int(_lib.lib().az_conv2d_stats_tiles(b, h, w, stats.groups))
-        part, cnt = xr.new_empty(stats.groups, cout, tiles, 2), xr.new_empty(stats.groups, tiles)
-        stats.part, stats.cnt, stats.tiles = part, cnt, tiles
-    with profiler.scope(f"{tag}_{kh}x{kw}d{dil}_{cin}_{cout}", flops=2.0 * kh * kw * cin * cout * b * h * w,
-                        peak=PEAK_X6):
-        if stats is not None:
-            _call("az_conv2d_fwd_stats", _p(out), _p(part), _p(cnt), _p(xr), _p(packed), stats.groups, b, h, w, cin, cout,
-                  cx, cout, kh, kw, dil, _stream())
-        else:
-            _call("az_conv2d_fwd", _p(out), _p(xr), _p(packed), _p(scale), _p(shift), _p(res), int(relu), b, h, w,
-                  cin, cout, cx, cout, res.shape[-1] if res is not None else 0, kh, kw, dil, _stream())
-    return out
-
-
 def _run_same(t, tr, weight, ci, co, kh, kw, dil, flip, f16, res=None, tag="conv2d", stats=None):
     """One stride-1 "same" launch ci -> co on the rows tr of the tensor t: picks the kernel (_roll_ok) and the arithmetic
     (f16), packs `weight` ([Cout,Cin,kh,kw]) for it and runs it.  flip = False: the layer's forward (ci, co = Cin, Cout);
@@ -215,23 +246,27 @@ def _run_same(t, tr, weight, ci, co, kh, kw, dil, flip, f16, res=None, tag="conv
     (ci, co = Cout, Cin)."""
     taps = kh * kw
     s_out, s_in = (taps, co * taps) if flip else (ci * taps, taps)  # strides of the co / ci index in the stored weight
-    roll = _roll_ok(tr, ci, co, kh, kw, dil, res)
-    if f16 and roll:
-        pk, w_amax = _pack_roll_f16(weight, ci, co, s_out, s_in, flip)
-        return _run_roll_f16(tr, _amax_of(t, tr), pk, w_amax, ci, co, res=res, tag=tag, stats=stats)
-    if f16:
-        pk, w_amax = _pack_f16(weight, ci, co, ci, co, s_out, s_in, kh, kw, flip)
-        return _run_f16(tr, _amax_of(t, tr), pk, w_amax, ci, co, kh, kw, dil, res=res, tag=tag, stats=stats)
-    if roll:
-        return _run_roll(tr, _pack_roll(weight, ci, co, s_out, s_in, flip), ci, co, res=res, tag=tag, stats=stats)
-    return _run(tr, _pack(weight, ci, co, ci, co, s_out, s_in, kh, kw, flip), ci, co, kh, kw, dil, res=res, tag=tag, stats=stats)
+    if _roll_ok(tr, ci, co, kh, kw, dil, res):
+        k = ROLL_F16 if f16 else ROLL_X6
+    else:
+        k = GATHER_F16 if f16 else GATHER_X6
+    pk, w_amax = _pack_image(k, weight, ci, co, s_out, s_in, kh, kw, flip)
+    return _launch(k, tr, pk, ci, co, kh, kw, dil, (_amax_of(t, tr), w_amax) if f16 else None, res=res, tag=tag, stats=stats)
 
 
-def _wgrad(gr, xr, cm, cn, cm_real, cn_real, kh, kw, dil, tag="conv2d", sink=None, amax=None, late_ok=True):
+# arithmetic -> (weight-gradient entry, its amax operands, whether kh, kw, dilation follow the strides, profiler peak)
+_WGRAD = {"bf16x6": ("az_conv2d_wgrad", NO_AMAX, True, PEAK_X6), "f16x3": ("az_conv2d_wgrad_f16", AMAX_TAKEN, True, PEAK_F16),
+          "bf16": ("az_conv2d_wgrad_bf16", NO_AMAX, False, PEAK_BF16), "f16x1": ("az_conv2d_wgrad_h1", AMAX_GIVEN, False, PEAK_BF16)}
+
+
+def _wgrad(gr, xr, cm, cn, cm_real, cn_real, kh, kw, dil, tag="conv2d", sink=None, amax=None, late_ok=True, arith=None):
     """gr: [B,H,W,>=cm] grad rows, xr: [B,H,W,>=cn] input rows -> [cm_real, cn_real, kh, kw].
     sink: overlap.Sink or None -- the kernels run on its side stream (the result is valid after its join).
     amax: None (bf16x6) or (amax array of gr or None, of xr or None): the f16x3 kernels; a missing one is taken here.
-    late_ok = False: the caller reads the result on the side stream right away: no deferred epilogue (overlap.Sink)."""
+    late_ok = False: the caller reads the result on the side stream right away: no deferred epilogue (overlap.Sink).
+    arith: a key of _WGRAD; None: by `amax`, as above.  "bf16" / "f16x1" (the ConvGRU's, 3x3 d1): one part per operand,
+    for f16x1 amax = (of gr, None); their scope is named `tag` + channels alone."""
+    entry, am_kind, geometry, peak = _WGRAD[arith or ("bf16x6" if amax is None else "f16x3")]
     b, h, w, _ = xr.shape
     gw = xr.new_empty(cm_real, cn_real, kh, kw)
     ws_bytes = _lib.lib().az_conv2d_wgrad_workspace(cm, cn, kh, kw)
@@ -243,20 +278,19 @@ def _wgrad(gr, xr, cm, cn, cm_real, cn_real, kh, kw, dil, tag="conv2d", sink=Non
         late = late_ok and sink is not None and sink.live and overlap.DEFER_UNPACK
         ws = sink.take_workspace(ws_bytes // 4) if late else xr.new_empty(ws_bytes // 4)
         out = None if late else _p(gw)
-        if amax is None:
-            with profiler.scope(f"{tag}_wgrad_{kh}x{kw}d{dil}_{cm}_{cn}", flops=2.0 * kh * kw * cm * cn * b * h * w,
-                                peak=PEAK_X6):
-                _call("az_conv2d_wgrad", out, _p(ws), ws_bytes, _p(gr), _p(xr), b, h, w, cm, cn, cm_real, cn_real,
-                      gr.shape[-1], xr.shape[-1], kh, kw, dil, _stream())
-        else:
-            am_g = amax[0] if amax[0] is not None else absmax(gr)
-            am_x = amax[1] if amax[1] is not None else absmax(xr)
-            with profiler.scope(f"{tag}_wgrad_{kh}x{kw}d{dil}_{cm}_{cn}", flops=2.0 * kh * kw * cm * cn * b * h * w,
-                                peak=PEAK_F16):
-                _call("az_conv2d_wgrad_f16", out, _p(ws), ws_bytes, _p(gr), _p(xr), _p(am_g), _p(am_x), b, h, w, cm, cn,
-                      cm_real, cn_real, gr.shape[-1], xr.shape[-1], kh, kw, dil, _stream())
-            if sink is not None and sink.live:
-                sink.keep.extend((am_g, am_x))
+        am = ()
+        if am_kind:
+            am_g, am_x = amax
+            if am_kind == AMAX_TAKEN:
+                am_g = am_g if am_g is not None else absmax(gr)
+                am_x = am_x if am_x is not None else absmax(xr)
+            am = (_p(am_g), _p(am_x))
+        name = f"{tag}_wgrad_{kh}x{kw}d{dil}_{cm}_{cn}" if geometry else f"{tag}_{cm}_{cn}"
+        with profiler.scope(name, flops=2.0 * kh * kw * cm * cn * b * h * w, peak=peak):
+            _call(entry, out, _p(ws), ws_bytes, _p(gr), _p(xr), *am, b, h, w, cm, cn, cm_real, cn_real, gr.shape[-1],
+                  xr.shape[-1], *((kh, kw, dil) if geometry else ()), _stream())
+        if am_kind and sink is not None and sink.live:
+            sink.keep.extend(t for t in (am_g, am_x) if t is not None)
         if late:
             sink.defer_unpack(gw, ws, cm, cn, cm_real, cn_real, kh * kw)
     return gw
@@ -266,11 +300,11 @@ _OVERLAP_2D = os.environ.get("AZ_2D_WGRAD_OVERLAP", "1") != "0"  # (scheduling e
 
 
 def _leaf_sink(sink, weight):
-    if not _OVERLAP_2D:
-        return None
     """A sink lets a weight gradient be handed to autograd before its kernel has run; that is only sound when
     the next reader is the pass's own gate node (overlap.py), i.e. when `weight` is one of the sink's gated
     parameters -- not for derived tensors such as the merged kernels of the cost-volume convolution."""
+    if not _OVERLAP_2D:
+        return None
     return sink if (sink is not None and sink.owns(weight)) else None
 
 
@@ -404,11 +438,11 @@ class _ConvS2Patches(torch.autograd.Function):
         w2 = weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous()
         with torch.cuda.device(x.device):
             _call("az_im2col_s2k3", _p(patches), _p(xr), b, cin, h, w, kp, _stream())
-            pk = _pack(w2, kp, cout, 9 * cin, cout, 9 * cin, 1, 1, 1, False)
+            pk, _ = _pack_image(GATHER_X6, w2, kp, cout, 9 * cin, 1, 1, 1, False, ci_real=9 * cin)
             if stats is not None and b % stats.groups == 0:
-                y = _run(patches, pk, kp, cout, 1, 1, 1, stats=stats)
+                y = _launch(GATHER_X6, patches, pk, kp, cout, 1, 1, 1, stats=stats)
             else:
-                y = _run(patches, pk, kp, cout, 1, 1, 1, tag="fe2d_first")
+                y = _launch(GATHER_X6, patches, pk, kp, cout, 1, 1, 1, tag="fe2d_first")
         ctx.save_for_backward(patches, w2)
         ctx.dims = (b, cin, h, w, kp)
         return image(y)
@@ -422,8 +456,8 @@ class _ConvS2Patches(torch.autograd.Function):
         gx = gw = None
         with torch.cuda.device(gy.device):
             if ctx.needs_input_grad[0]:
-                pk = _pack(w2, cout, kp, cout, 9 * cin, 1, 9 * cin, 1, 1, True)
-                gp = _run(gr, pk, cout, kp, 1, 1, 1, tag="dgrad2d_first")
+                pk, _ = _pack_image(GATHER_X6, w2, cout, kp, 1, 9 * cin, 1, 1, True, co_real=9 * cin)
+                gp = _launch(GATHER_X6, gr, pk, cout, kp, 1, 1, 1, tag="dgrad2d_first")
                 gxr = gr.new_empty(b, h, w, cin)
                 _call("az_col2im_s2k3", _p(gxr), _p(gp), b, cin, h, w, kp, _stream())
                 gx = image(gxr)
@@ -488,5 +522,6 @@ def conv_bn_eval(x, m, bn, relu=False, residual=None):
         #  on where that floor comes from).  Train-mode BatchNorm subtracts it with the batch mean; with the
         #  running-statistics map of inference it survives the 64x64 SPP averages, and the full-size eval output moved
         #  from 7.0e-4 to 1.05e-3 px max error against the exact result -- over the 1e-3 bar -- for 16 % less latency.)
-        pk = _pack(m.weight, cin, cout, cin, cout, cin * kh * kw, kh * kw, kh, kw, False, cache=True)
-        return image(_run(xr, pk, cin, cout, kh, kw, d[0] if kh > 1 else 1, scale, shift, rr, relu, tag="conv2d_eval"))
+        pk, _ = _pack_image(GATHER_X6, m.weight, cin, cout, cin * kh * kw, kh * kw, kh, kw, False, cache=True)
+        return image(_launch(GATHER_X6, xr, pk, cin, cout, kh, kw, d[0] if kh > 1 else 1, None, scale, shift, rr, relu,
+                             tag="conv2d_eval"))

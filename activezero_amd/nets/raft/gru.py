@@ -28,12 +28,12 @@ import weakref
 import torch
 import torch.nn as nn
 
-from activezero_amd import _lib, amax, conv2d, profiler
+from activezero_amd import amax, conv2d
 from activezero_amd.packing import CACHE_LOCK, cache_get, cache_key, cache_put, memo
 from activezero_amd.ops import _call, _chk, _p, _stream
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, ACT_GRU = range(5)
-PEAK_BF16 = (2500.0, "dense bf16 MFMA peak")
+_ARITH = ("bf16", "f16x1")  # by `h1`: the names of the one-part arithmetics in profiler scopes and conv2d._WGRAD
 _PACK_CACHE = {}
 _CTX_CACHE = {}
 CTX_CONVERSIONS = 0  # context-row conversions so far (tests: one per step and GRU level, whatever the inputs' dtype)
@@ -128,18 +128,24 @@ def _assemble(h, xs):
     return hx, [s[1] == 1 for s in srcs[1:]]
 
 
-def _pack_bf16(weights, cache):
-    """[Cout_i, Cin, 3, 3] weights (concatenated along Cout) -> the kernel's one-part bf16 image."""
+def _pack(weights, k, flipped=False, cache=True):
+    """[Cout_i, Cin, 3, 3] weights (concatenated along Cout) -> the one-part image of kernel k (conv2d.ONE_BF16 / ONE_H1):
+    the forward's, or with flipped = True the input gradient's (taps flipped, channel roles swapped); unscaled, as
+    autocast casts them.  cache = False: not memoised (the call site has autograd on a derived weight)."""
     def make():
         w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
-        cout, cin, kh, kw = w.shape
-        if _lib.lib().az_conv2d_packed_floats(cin, cout, kh, kw) < 0:
+        cout, cin = w.shape[0], w.shape[1]
+        if not flipped and (cin % 16 or cout % 32):  # (the flipped image's counts: the library's own check)
             raise RuntimeError(f"ConvGRU: unsupported channel counts cin={cin} cout={cout} (need cin % 16 == 0, cout % 32 == 0)")
-        packed = torch.empty(kh * kw * cin * cout // 2, dtype=torch.float32, device=w.device)
-        _call("az_conv2d_pack_weights_bf16", _p(packed), _p(w), cin, cout, cin * kh * kw, kh * kw, kh, kw, _stream())
-        return packed
+        if flipped:
+            return conv2d._pack_image(k, w, cout, cin, 9, cin * 9, 3, 3, True)[0]
+        return conv2d._pack_image(k, w, cin, cout, cin * 9, 9, 3, 3, False)[0]
 
-    return memo(_PACK_CACHE, cache_key(*weights) if cache else None, make, tuple(weights), 64)
+    return memo(_PACK_CACHE, (k.fwd, bool(flipped)) + cache_key(*weights) if cache else None, make, tuple(weights), 64)
+
+
+def _pack_bf16(weights, cache):
+    return _pack(weights, conv2d.ONE_BF16, False, cache)
 
 
 def conv3x3_bf16(xr, packed, cin, cout, bias=None, residual=None, act=ACT_NONE, gate_z=None, gate_h=None, h1=False,
@@ -147,33 +153,9 @@ def conv3x3_bf16(xr, packed, cin, cout, bias=None, residual=None, act=ACT_NONE, 
     """xr [B,H,W,>=cin] fp32 rows -> act(conv3x3(xr[..., :cin]) + bias + residual) as [B,H,W,cout] rows.
     h1: one FP16 part per operand (az_conv2d_h1_fwd; `packed` from az_conv2d_pack_weights_h1) instead of one bf16 part;
     in_amax: amax array of xr for a power-of-two operand scale (gradient operands), None = rounded as it is."""
-    b, h, w, cx = xr.shape
-    out = xr.new_empty(b, h, w, cout)
-    tail = (act, b, h, w, cin, cout, cx, cout, residual.shape[-1] if residual is not None else 0,
-            gate_z.shape[-1] if gate_z is not None else 0, gate_h.shape[-1] if gate_h is not None else 0, _stream())
-    with profiler.scope(f"gru_conv3x3_{'f16x1' if h1 else 'bf16'}_{cin}_{cout}", flops=18.0 * cin * cout * b * h * w, peak=PEAK_BF16):
-        if h1:
-            _call("az_conv2d_h1_fwd", _p(out), _p(xr), _p(packed), _p(in_amax), None, _p(bias), _p(residual), _p(gate_z),
-                  _p(gate_h), *tail)
-        else:
-            _call("az_conv2d_bf16_fwd", _p(out), _p(xr), _p(packed), _p(bias), _p(residual), _p(gate_z), _p(gate_h), *tail)
-    return out
-
-
-def _pack_h1(weights, flipped, cache=True):
-    """one-part FP16 image (forward, or the input gradient's with flipped = True) of [Cout_i, Cin, 3, 3] weights
-    concatenated along Cout; unscaled, as autocast casts them"""
-    def make():
-        w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
-        cout, cin = w.shape[0], w.shape[1]
-        packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=w.device)
-        if flipped:
-            _call("az_conv2d_pack_weights_h1", _p(packed), _p(w), None, cout, cin, 9, cin * 9, 1, _stream())
-        else:
-            _call("az_conv2d_pack_weights_h1", _p(packed), _p(w), None, cin, cout, cin * 9, 9, 0, _stream())
-        return packed
-
-    return memo(_PACK_CACHE, ("h1", bool(flipped)) + cache_key(*weights) if cache else None, make, tuple(weights), 64)
+    k, am = (conv2d.ONE_H1, (in_amax, None)) if h1 else (conv2d.ONE_BF16, None)
+    return conv2d._launch(k, xr, packed, cin, cout, amax=am, res=residual, bias=bias, act=act,
+                          tag=f"gru_conv3x3_{_ARITH[h1]}", gates=(gate_z, gate_h))
 
 
 def _rows(t):
@@ -188,11 +170,9 @@ class _Conv3x3Bf16(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         xr = _chk(conv2d.rows(x), "x")
         cout, cin = weight.shape[0], weight.shape[1]
-        w = weight.detach().float().contiguous()
-        packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=w.device)
         with torch.cuda.device(x.device):
-            _call("az_conv2d_pack_weights_bf16", _p(packed), _p(w), cin, cout, cin * 9, 9, 3, 3, _stream())
-            y = conv3x3_bf16(xr, packed, cin, cout, bias.detach().float().contiguous() if bias is not None else None)
+            y = conv3x3_bf16(xr, _pack((weight,), conv2d.ONE_BF16, cache=False), cin, cout,
+                             bias.detach().float().contiguous() if bias is not None else None)
         ctx.save_for_backward(xr, weight)
         ctx.has_bias = bias is not None
         return conv2d.image(y)
@@ -202,36 +182,15 @@ class _Conv3x3Bf16(torch.autograd.Function):
         xr, weight = ctx.saved_tensors
         cout, cin = weight.shape[0], weight.shape[1]
         gr = _chk(conv2d.rows(gy), "grad_y")
-        b, h, w_, _ = xr.shape
         gx = gw = gb = None
         with torch.cuda.device(gy.device):
-            wt = weight.detach().float().contiguous()
             if ctx.needs_input_grad[0]:  # the same convolution on gy with flipped taps and swapped channel roles
-                packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=wt.device)
-                _call("az_conv2d_pack_weights_bf16_flipped", _p(packed), _p(wt), cout, cin, 9, cin * 9, 3, 3, _stream())
-                gx = conv2d.image(conv3x3_bf16(gr, packed, cout, cin))
+                gx = conv2d.image(conv3x3_bf16(gr, _pack((weight,), conv2d.ONE_BF16, True, cache=False), cout, cin))
             if ctx.needs_input_grad[1]:
-                gw = xr.new_empty(cout, cin, 3, 3)
-                ws_bytes = _lib.lib().az_conv2d_wgrad_workspace(cout, cin, 3, 3)
-                ws = xr.new_empty(ws_bytes // 4)
-                with profiler.scope(f"gru_wgrad_bf16_{cout}_{cin}", flops=18.0 * cin * cout * b * h * w_, peak=PEAK_BF16):
-                    _call("az_conv2d_wgrad_bf16", _p(gw), _p(ws), ws_bytes, _p(gr), _p(xr), b, h, w_, cout, cin, cout, cin,
-                          gr.shape[-1], xr.shape[-1], _stream())
+                gw = conv2d._wgrad(gr, xr, cout, cin, cout, cin, 3, 3, 1, tag="gru_wgrad_bf16", arith="bf16")
             if ctx.has_bias and ctx.needs_input_grad[2]:
                 gb = gr.sum(dim=(0, 1, 2))
         return gx, gw, gb
-
-
-def _pack_bf16_flipped(weights, cache):
-    """the one-part bf16 image of the INPUT-gradient convolution of [Cout_i, Cin, 3, 3] weights (concatenated along Cout)"""
-    def make():
-        w = torch.cat([x.detach().float() for x in weights], 0).contiguous()
-        cout, cin = w.shape[0], w.shape[1]
-        packed = torch.empty(9 * cin * cout // 2, dtype=torch.float32, device=w.device)
-        _call("az_conv2d_pack_weights_bf16_flipped", _p(packed), _p(w), cout, cin, 9, cin * 9, 3, 3, _stream())
-        return packed
-
-    return memo(_PACK_CACHE, ("flip",) + cache_key(*weights) if cache else None, make, tuple(weights), 64)
 
 
 class _GRUStepBf16(torch.autograd.Function):
@@ -245,7 +204,7 @@ class _GRUStepBf16(torch.autograd.Function):
         """h1: True = "f16x1" (one fp16 part per operand: the reference's float16 autocast), False = "bf16".
         czr / cqr: the fp32 rows of the context terms (`_context_rows`; cz / cr / cq themselves only receive gradients)"""
         ctx.h1 = h1
-        pk = (lambda ws: _pack_h1(ws, False)) if h1 else (lambda ws: _pack_bf16(ws, True))
+        k = conv2d.ONE_H1 if h1 else conv2d.ONE_BF16
         c, ci = h.shape[1], sum(t.shape[1] for t in xs)
         with torch.cuda.device(h.device):
             b, _, hh, ww = h.shape
@@ -253,10 +212,10 @@ class _GRUStepBf16(torch.autograd.Function):
             hx, as_image = _assemble(h, xs)  # [h | x_0 | x_1 ..] rows in one launch (az_rows_concat)
             ctx.as_image = as_image
             bzr = torch.cat([bz, br]).detach().float().contiguous()
-            zr = conv3x3_bf16(hx, pk((wz, wr)), c + ci, 2 * c, bzr, czr, ACT_SIGMOID, h1=h1)
+            zr = conv3x3_bf16(hx, _pack((wz, wr), k), c + ci, 2 * c, bzr, czr, ACT_SIGMOID, h1=h1)
             rhx = torch.empty_like(hx)
             _call("az_gru_rh", _p(rhx), _p(zr), _p(hx), npix, c, ci, _stream())
-            q = conv3x3_bf16(rhx, pk((wq,)), c + ci, c, bq.detach().float().contiguous(), cqr, ACT_TANH, h1=h1)
+            q = conv3x3_bf16(rhx, _pack((wq,), k), c + ci, c, bq.detach().float().contiguous(), cqr, ACT_TANH, h1=h1)
             hn = torch.empty_like(q)
             _call("az_gru_out", _p(hn), _p(zr), _p(q), _p(hx), npix, c, ci, _stream())
         ctx.save_for_backward(hx, rhx, zr, q, wz, wr, wq)
@@ -290,27 +249,18 @@ class _GRUStepBf16(torch.autograd.Function):
             # them) before the fp16 rounding -- the job GradScaler does for the reference (train.py:303-309)
             am_q = amax.ZEROS.take(q) if h1 else None
             am_z = amax.ZEROS.take(q) if h1 else None
-            pkf = (lambda ws: _pack_h1(ws, True)) if h1 else (lambda ws: _pack_bf16_flipped(ws, True))
+            k = conv2d.ONE_H1 if h1 else conv2d.ONE_BF16
             _call("az_gru_bwd1", _p(dq), _p(dzr), _p(dh_acc), _p(g), _p(zr), _p(q), _p(hx), npix, c, ci, _p(am_q), _p(am_z), _stream())
-            d_rhx = conv3x3_bf16(dq, pkf((wq,)), c, ct, h1=h1, in_amax=am_q)
+            d_rhx = conv3x3_bf16(dq, _pack((wq,), k, True), c, ct, h1=h1, in_amax=am_q)
             _call("az_gru_bwd2", _p(dzr), _p(dh_acc), _p(d_rhx), _p(zr), _p(hx), npix, c, ci, _p(am_z), _stream())
-            d_hx = conv3x3_bf16(dzr, pkf((wz, wr)), 2 * c, ct, h1=h1, in_amax=am_z)
+            d_hx = conv3x3_bf16(dzr, _pack((wz, wr), k, True), 2 * c, ct, h1=h1, in_amax=am_z)
             dh = torch.empty_like(q)
             dx = hx.new_empty(b, hh, ww, ci)
             _call("az_gru_bwd3", _p(dh), _p(dx), _p(dh_acc), _p(d_rhx), _p(d_hx), npix, c, ci, _stream())
 
             def wgrad(go, xin, cout, go_amax):
-                gw = hx.new_empty(cout, ct, 3, 3)
-                ws_bytes = _lib.lib().az_conv2d_wgrad_workspace(cout, ct, 3, 3)
-                ws = hx.new_empty(ws_bytes // 4)
-                with profiler.scope(f"gru_wgrad_{'f16x1' if h1 else 'bf16'}_{cout}_{ct}", flops=18.0 * ct * cout * npix, peak=PEAK_BF16):
-                    if h1:
-                        _call("az_conv2d_wgrad_h1", _p(gw), _p(ws), ws_bytes, _p(go), _p(xin), _p(go_amax), None, b, hh, ww, cout, ct,
-                              cout, ct, go.shape[-1], xin.shape[-1], _stream())
-                    else:
-                        _call("az_conv2d_wgrad_bf16", _p(gw), _p(ws), ws_bytes, _p(go), _p(xin), b, hh, ww, cout, ct, cout, ct,
-                              go.shape[-1], xin.shape[-1], _stream())
-                return gw
+                return conv2d._wgrad(go, xin, cout, ct, cout, ct, 3, 3, 1, tag=f"gru_wgrad_{_ARITH[h1]}",
+                                     amax=(go_amax, None) if h1 else None, arith=_ARITH[h1])
 
             gwz = gwr = gwq = gbz = gbr = gbq = None
             if need[7] or need[8]:
@@ -386,10 +336,10 @@ class ConvGRU(nn.Module):
                 at += x.shape[1]
             czr = torch.cat([cz.permute(0, 2, 3, 1), cr.permute(0, 2, 3, 1)], -1).float().contiguous()
             bzr = torch.cat([self.convz.bias, self.convr.bias]).detach().float().contiguous()
-            zr = conv3x3_bf16(hx, _pack_bf16((self.convz.weight, self.convr.weight), True), ct, 2 * c, bzr, czr,
+            zr = conv3x3_bf16(hx, _pack((self.convz.weight, self.convr.weight), conv2d.ONE_BF16), ct, 2 * c, bzr, czr,
                               ACT_SIGMOID)
             hx[..., :c] = zr[..., c:] * hr
-            out = conv3x3_bf16(hx, _pack_bf16((self.convq.weight,), True), ct, c,
+            out = conv3x3_bf16(hx, _pack((self.convq.weight,), conv2d.ONE_BF16), ct, c,
                                self.convq.bias.detach().float().contiguous(), _rows(cq), ACT_GRU, gate_z=zr, gate_h=hr)
         return out.permute(0, 3, 1, 2)
 

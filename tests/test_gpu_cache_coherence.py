@@ -6,9 +6,10 @@ Sites (one small call each, through the entry point the networks use):
                    (1, 4, 8, 16): PACK_CACHE through _pack and _pack_f16, AFFINE_CACHE, _W_AMAX;
   * costvol        LazyCostVolume into agg3d.conv_bn (the eval path of dres0[0]);
   * eval2d_*       the extractor's conv+BatchNorm unit in eval mode: conv2d.conv_bn_eval for the 3x3 and 1x1 32-multiple layers
-                   (_PACK2D_CACHE through _pack, AFFINE_CACHE), the generic route for the 3-channel stride-2 first layer;
-                   conv2d's _pack_f16 and _pack_roll have no memoised caller today, so pack2d_* call them with cache=True
-                   directly (1x1 40 -> 12 with padded channel counts, 3x3 32 -> 32) and compare image bytes;
+                   (_PACK2D_CACHE through _pack_image, AFFINE_CACHE), the generic route for the 3-channel stride-2 first layer;
+                   only the gather bf16x6 row of conv2d.KERNELS has a memoised caller today, so pack2d_* call
+                   conv2d._pack_image with cache=True directly for the gather f16x3 and roll bf16x6 rows too (1x1 40 -> 12 with
+                   padded channel counts, 3x3 32 -> 32) and compare image bytes;
   * merged         costconv._merged_kernels under no_grad (_MERGED_CACHE);  weight_amax: amax.weight_amax (_W_AMAX);
   * train3d_*      the training forward of a unit after packing.prepack + amax.prime_weight_amax, as PSMNet's pass does
                    (PackPlan's entries, amax_rows, _PRIME_ROWS, _W_AMAX).  Train-mode outputs pass through float atomics
@@ -134,18 +135,18 @@ def _weight_amax_call(mod, _):
 
 def _pack2d_f16_call(mod, _):  # 1x1 40 -> 12: channel counts padded to 48 / 32, as tests/test_gpu_pack_plan.py packs it
     with torch.no_grad():
-        packed, w_amax = conv2d._pack_f16(mod.weight, 48, 32, 40, 12, 40, 1, 1, 1, False, cache=True)
+        packed, w_amax = conv2d._pack_image(conv2d.GATHER_F16, mod.weight, 48, 32, 40, 1, 1, 1, False, 40, 12, cache=True)
         return packed, _amax_value(w_amax)
 
 
 def _pack2d_roll_call(mod, _):
     with torch.no_grad():
-        return conv2d._pack_roll(mod.weight, 32, 32, 32 * 9, 9, False, cache=True)
+        return conv2d._pack_image(conv2d.ROLL_X6, mod.weight, 32, 32, 32 * 9, 9, cache=True)[0]
 
 
 def _pack2d_call(mod, _):
     with torch.no_grad():
-        return conv2d._pack(mod.weight, 48, 32, 40, 12, 40, 1, 1, 1, False, cache=True)
+        return conv2d._pack_image(conv2d.GATHER_X6, mod.weight, 48, 32, 40, 1, 1, 1, False, 40, 12, cache=True)[0]
 
 
 def _handed(unit, x, arith="f16x3"):

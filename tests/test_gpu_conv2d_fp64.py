@@ -191,6 +191,14 @@ def run_conv(kind, cin, cout, arith, geom, src, wt, res=None):
         return nchw(conv2d._run_same(src, src, wt, ci, co, geom.kh, geom.kw, geom.dil, flip, arith == "f16x3", res=res))
 
 
+def launch(k, xr, wd, cin, cout, x_amax=None, **epilogue):
+    """a 3x3 d1 layer's forward on the kernel of row k of conv2d.KERNELS, whatever conv2d._run_same would route it to"""
+    with torch.no_grad():
+        pk, w_am = conv2d._pack_image(k, wd, cin, cout, cin * 9, 9)
+        return conv2d._launch(k, xr, pk, cin, cout, amax=(x_amax if x_amax is not None else amax.absmax(xr), w_am) if k.amax else None,
+                              **epilogue)
+
+
 def run_wgrad(cin, cout, arith, geom, xr, gr):
     with torch.no_grad():
         return conv2d._wgrad(gr, xr, cout, cin, cout, cin, geom.kh, geom.kw, geom.dil,
@@ -300,9 +308,7 @@ def test_roll_affine_relu_epilogue_bf16x6(cin, cout, shape, capsys):
     sc[::5] *= -1.0
     res = seeded((b, cout, h, w), 7962) * 0.5
     name = route_conv(cin, cout, "bf16x6", shape, G33, "epi", force_roll=True)
-    pk = conv2d._pack_roll(wt.to(DEV), cin, cout, cin * 9, 9, False)
-    with torch.no_grad():
-        got = nchw(conv2d._run_roll(rows(x), pk, cin, cout, scale=sc.to(DEV), shift=sh.to(DEV), res=rows(res), relu=True))
+    got = nchw(launch(conv2d.ROLL_X6, rows(x), wt.to(DEV), cin, cout, scale=sc.to(DEV), shift=sh.to(DEV), res=rows(res), relu=True))
     r = verdict(got, "fwd", cin, cout, shape, G33, "bf16x6", epilogue=(sc, sh, res, True))
     record("bf16x6", "fwd", f"fwd affine+relu+res {cin}->{cout} {shape} [{name}]", r, capsys)
     assert max(r) <= 1.0, (name, r)
@@ -326,12 +332,8 @@ def test_generic_kernel_with_wide_pixel_strides(arith, which, capsys):
     name = route_conv(cin, cout, arith, shape, geom, "res" if res is not None else "plain", cx=xr.shape[-1],
                       res_c=rr.shape[-1] if rr is not None else None)
     assert "generic" in name
-    with torch.no_grad():
-        if arith == "f16x3":
-            pk, w_am = conv2d._pack_f16(wt.to(DEV), cin, cout, cin, cout, cin * 9, 9, 3, 3, False)
-            out = conv2d._run_f16(xr, amax.absmax(rows(x)), pk, w_am, cin, cout, 3, 3, 1, res=rr)
-        else:
-            out = conv2d._run(xr, conv2d._pack(wt.to(DEV), cin, cout, cin, cout, cin * 9, 9, 3, 3, False), cin, cout, 3, 3, 1, res=rr)
+    k = conv2d.KERNELS[f"gather {arith}"]
+    out = launch(k, xr, wt.to(DEV), cin, cout, x_amax=amax.absmax(rows(x)) if k.amax else None, res=rr)
     r = verdict(nchw(out), "fwd", cin, cout, shape, geom, arith, addend=res)
     record(arith, "fwd", f"fwd {which}-stride 96 {cin}->{cout} {shape} [{name}]", r, capsys)
     assert max(r) <= 1.0, (name, r)
@@ -351,14 +353,10 @@ def test_roll_stats_partials_on_a_batch_walk(cin, cout, shape, groups, arith, ca
     part = torch.full((groups, cout, nrows, 2), float("nan"), device=DEV)
     cnt = torch.full((groups, nrows), float("nan"), device=DEV)
     out = torch.empty(b, h, w, cout, device=DEV)
-    if arith == "f16x3":
-        pk, w_am = conv2d._pack_roll_f16(wd, cin, cout, cin * 9, 9, False)
-        x_am = amax.absmax(xr)
-        _call("az_conv2d_roll_fwd_stats_f16", _p(out), _p(part), _p(cnt), _p(xr), _p(pk), _p(x_am), _p(w_am), groups, b, h, w,
-              cin, cout, _stream())
-    else:
-        pk = conv2d._pack_roll(wd, cin, cout, cin * 9, 9, False)
-        _call("az_conv2d_roll_fwd_stats", _p(out), _p(part), _p(cnt), _p(xr), _p(pk), groups, b, h, w, cin, cout, _stream())
+    k = conv2d.KERNELS[f"roll {arith}"]
+    pk, w_am = conv2d._pack_image(k, wd, cin, cout, cin * 9, 9)
+    am = (_p(amax.absmax(xr)), _p(w_am)) if k.amax else ()
+    _call(k.stats[0], _p(out), _p(part), _p(cnt), _p(xr), _p(pk), *am, groups, b, h, w, cin, cout, _stream())
     torch.cuda.synchronize()
     r = verdict(nchw(out), "fwd", cin, cout, shape, G33, arith)
     record(arith, "fwd", f"fwd+stats {cin}->{cout} {shape} groups {groups} [{name}]", r, capsys)

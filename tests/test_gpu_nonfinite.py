@@ -426,14 +426,8 @@ def test_conv2d_epilogues(how, cin, cout, arith, relu):
         with torch.no_grad():
             if how == "same":
                 return C2.run_conv("fwd", cin, cout, arith, C2.G33, xr, wd, res=rr)
-            if how == "roll":
-                pk = conv2d._pack_roll(wd, cin, cout, cin * 9, 9, False)
-                return C2.nchw(conv2d._run_roll(xr, pk, cin, cout, scale=scd, shift=shd, res=rr, relu=relu))
-            if arith == "f16x3":
-                pk, w_am = conv2d._pack_f16(wd, cin, cout, cin, cout, cin * 9, 9, 3, 3, False)
-                return C2.nchw(conv2d._run_f16(xr, amax.absmax(xr), pk, w_am, cin, cout, 3, 3, 1, scale=scd, shift=shd, res=rr, relu=relu))
-            pk = conv2d._pack(wd, cin, cout, cin, cout, cin * 9, 9, 3, 3, False)
-            return C2.nchw(conv2d._run(xr, pk, cin, cout, 3, 3, 1, scale=scd, shift=shd, res=rr, relu=relu))
+            k = conv2d.KERNELS[f"{'roll' if how == 'roll' else 'gather'} {arith}"]
+            return C2.nchw(C2.launch(k, xr, wd, cin, cout, scale=scd, shift=shd, res=rr, relu=relu))
 
     epilogue_case(f"2-D {cin}->{cout} {arith} relu={relu} [{name}]", x, launch,
                   C2.reference("fwd", cin, cout, C2_SHAPE, C2.G33)["y"].cpu(), CONV2, sc, sh, relu)

@@ -55,10 +55,11 @@ for name, cin, cout, k, dil, h, w, cnt in LAYERS:
     else:
         xr, gr = conv2d.rows(x), conv2d.rows(gy)
         T = k * k
-        pf = conv2d._pack(wt, cin, cout, cin, cout, cin * T, T, k, k, False)
-        pd = conv2d._pack(wt, cout, cin, cout, cin, T, cin * T, k, k, True)
-        f = lambda: conv2d._run(xr, pf, cin, cout, k, k, dil)
-        d = lambda: conv2d._run(gr, pd, cout, cin, k, k, dil)
+        K = conv2d.GATHER_X6
+        pf, _ = conv2d._pack_image(K, wt, cin, cout, cin * T, T, k, k, False)
+        pd, _ = conv2d._pack_image(K, wt, cout, cin, T, cin * T, k, k, True)
+        f = lambda: conv2d._launch(K, xr, pf, cin, cout, k, k, dil)
+        d = lambda: conv2d._launch(K, gr, pd, cout, cin, k, k, dil)
         g = lambda: conv2d._wgrad(gr, xr, cout, cin, cout, cin, k, k, dil)
     ms = [timeit(f), timeit(d), timeit(g)]
     for i in range(3):

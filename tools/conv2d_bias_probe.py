@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from activezero_amd import _lib, conv2d
 from activezero_amd.ops import _call, _p, _stream
 dev = torch.device("cuda:0"); lib = _lib.lib()
@@ -12,7 +12,7 @@ for (B, H, W, cin, cout) in ((8, 136, 240, 64, 64), (8, 272, 480, 32, 32)):
     _call("az_conv2d_roll_pack", _p(pk), _p(w), cin, cout, cin * 9, 9, 0, _stream())
     out = torch.empty(B, H, W, cout, device=dev)
     _call("az_conv2d_roll_fwd", _p(out), _p(x), _p(pk), None, None, None, 0, B, H, W, cin, cout, _stream())
-    pk_old = conv2d._pack(w, cin, cout, cin, cout, cin * 9, 9, 3, 3, False)
+    pk_old, _ = conv2d._pack_image(conv2d.GATHER_X6, w, cin, cout, cin * 9, 9)
     os.environ["X"] = "1"
     old = torch.empty(B, H, W, cout, device=dev)
     _call("az_conv2d_fwd", _p(old), _p(x), _p(pk_old), None, None, None, 0, B, H, W, cin, cout, cin, cout, 0, 3, 3, 1, _stream())

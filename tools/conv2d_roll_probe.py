@@ -33,8 +33,8 @@ for (B, H, W, cin, cout) in ((8, 272, 480, 32, 32), (8, 136, 240, 64, 64), (8, 1
     _call("az_conv2d_roll_fwd", _p(out), _p(x), _p(pk), None, None, _p(res), 1, B, H, W, cin, cout, _stream())
     e1 = float((out.double() - (ref + res.double()).clamp_min(0)).abs().max())
     # the library's current kernel
-    pk_old = conv2d._pack(w, cin, cout, cin, cout, cin * 9, 9, 3, 3, False)
-    old = conv2d._run(x, pk_old, cin, cout, 3, 3, 1)
+    pk_old, _ = conv2d._pack_image(conv2d.GATHER_X6, w, cin, cout, cin * 9, 9)
+    old = conv2d._launch(conv2d.GATHER_X6, x, pk_old, cin, cout)
     e_old = float((old.double() - ref).abs().max())
     e32 = float((torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), w, padding=1).permute(0, 2, 3, 1).double() - ref).abs().max())
     # statistics
@@ -54,7 +54,7 @@ for (B, H, W, cin, cout) in ((8, 272, 480, 32, 32), (8, 136, 240, 64, 64), (8, 1
     gf = 2.0 * 9 * cin * cout * B * H * W / 1e9
     t_new = timeit(lambda: _call("az_conv2d_roll_fwd", _p(out), _p(x), _p(pk), None, None, None, 0, B, H, W, cin, cout, _stream()))
     t_st = timeit(lambda: _call("az_conv2d_roll_fwd_stats", _p(out), _p(part), _p(cnt), _p(x), _p(pk), groups, B, H, W, cin, cout, _stream()))
-    t_old = timeit(lambda: conv2d._run(x, pk_old, cin, cout, 3, 3, 1))
+    t_old = timeit(lambda: conv2d._launch(conv2d.GATHER_X6, x, pk_old, cin, cout))
     print(f"[{B},{H},{W}] {cin}->{cout}: max|err| plain {e0:.2e} res+relu {e1:.2e} stats-run {e2:.2e} (current kernel {e_old:.2e}, torch fp32 {e32:.2e}); "
           f"count {int(n.sum())} of {B * H * W}, mean err {es:.1e} sigma, var rel err {ev:.1e}")
     print(f"      roll {t_new * 1e3:6.1f} us = {gf / t_new:6.1f} TFLOP/s ({gf / t_new / 416.7:.2f}); +stats {t_st * 1e3:6.1f} us; current {t_old * 1e3:6.1f} us ({gf / t_old / 416.7:.2f})")
